@@ -19,9 +19,13 @@ objects per GPU); for N > 1 the same run also measures the configuration as writ
 over the N ranks, balanced by the sum of modes) and reports it under "strong".
 
 One "step" = one pbso_step(86): host bookkeeping of ModalSolver::step for every (object, buffer), upload
-of the plan, projection, force combination, and the oscillator-bank kernel.  After the clock has stopped,
-8 objects of the first timed step are checked against the fp64 oracle (the run's own output, not a
-replay).  Prints ONE JSON line on rank 0.
+of the plan, projection, force combination, and the oscillator-bank kernel.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and no more: set-up, settle + warm-up steps, the timed steps, the
+line.  --full adds everything else the line has carried: the fp64 oracle check of 8 objects of the first
+timed step (the run's own output, not a replay), delivery to the host, the other block form, the strong-
+scaling shares, the one-second-step leg, the CPU baseline and, for N > 1, the side leg and the gather-cost
+legs.  --dump-outputs DIR writes a fixed, seeded sample of the last timed step's audio as .npy files.
 """
 import argparse
 import json
@@ -142,6 +146,14 @@ def parse(argv=None):
                          "mixed_precision_projection; headline block_bf16 -> exact_f32_projection), reported beside the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-objects", type=int, default=0, help="objects in the CPU baseline sample (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the oracle check, delivery to the host, the other block form, the "
+                         "strong-scaling shares, the one-second-step leg, the CPU baseline and, for N > 1, the side leg and the gather-"
+                         "cost legs (each still subject to its --no-... switch).  Off by default: a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- every object's audio -- as a fixed, seeded sample "
+                         "of at most 64 MB: DIR/audio_rows.npy (whole rows of some objects, float32), DIR/audio_row_ids.npy (their "
+                         "object ids, float64) and DIR/audio_samples.npy (single samples spread over all objects, float32); rank 0")
     args = ap.parse_args(argv)
     args.settle_auto = args.settle < 0
     if args.settle < 0:
@@ -185,15 +197,16 @@ def spawn_ranks(n, argv):
 # ----------------------------------------------------------------------------------------------------
 def build_inputs(args, global_ids, total_buffers):
     """Deterministic inputs per GLOBAL object id: eigenvalues, mode shapes and the scenario's script (hit vertices and
-    normals; scraping: one face hit per buffer; listener: FFAT maps and a listener position per buffer)."""
+    normals; scraping: one face hit per buffer; listener: FFAT maps and a listener position per buffer).
+    Every object draws from generators of its own, so the objects are made on a few threads (numpy's generators
+    release the GIL) with the same values as one by one: 1024 x 512 mode shapes alone take ~8 s on one thread."""
+    from concurrent.futures import ThreadPoolExecutor
     from openpbso_amd import synth
     M = args.modes
-    lam = np.empty((len(global_ids), M))
-    shapes, scripts = [], []
-    for i, gid in enumerate(global_ids):
+
+    def one(i, gid):
         seed = synth.seed_for(4, gid)
-        lam[i] = synth.eigenvalues(M, seed)
-        shapes.append(synth.mode_shapes(M, seed))
+        lam_i = synth.eigenvalues(M, seed)
         sc = {"hits": synth.poisson_hits(total_buffers, seed), "vns": synth.unit_normals(total_buffers, seed)}
         if args.scenario == "scraping":
             rng = np.random.default_rng(synth.seed_for(5, gid))
@@ -201,10 +214,49 @@ def build_inputs(args, global_ids, total_buffers):
             sc["bary"] = bary / bary.sum(axis=1, keepdims=True)
             sc["fids"] = rng.integers(0, synth.N_VERTS, (total_buffers, 3))
         elif args.scenario == "listener":
-            sc["maps"] = synth.ffat_maps(lam[i], synth.seed_for(3, gid))
+            sc["maps"] = synth.ffat_maps(lam_i, synth.seed_for(3, gid))
             sc["path"] = synth.listener_path(total_buffers) * (1.0 + 0.001 * i)
-        scripts.append(sc)
-    return lam, shapes, scripts
+        return lam_i, synth.mode_shapes(M, seed), sc
+
+    with ThreadPoolExecutor(max_workers=max(1, min(16, host_cores(), len(global_ids)))) as ex:
+        made = list(ex.map(one, range(len(global_ids)), global_ids))
+    lam = np.empty((len(global_ids), M))
+    for i, (lam_i, _, _) in enumerate(made):
+        lam[i] = lam_i
+    return lam, [x[1] for x in made], [x[2] for x in made]
+
+
+DUMP_SEED = 0xD0D0
+DUMP_ROWS = 16                      # whole rows of this many objects ...
+DUMP_ROW_FLOATS = 12 << 20          # ... 48 MB at most (fewer samples of each row beyond that)
+DUMP_SAMPLES = 1 << 20              # + 4 MB of single samples spread over every object
+
+
+def last_step_sample(eng, n_obj):
+    """What the timed path handed its caller in its last step -- every object's audio, [objects][buffers * 513] float32 --
+    as a fixed, seeded sample: whole rows of DUMP_ROWS objects and DUMP_SAMPLES single samples drawn over all of them.  Read
+    through pbso_read_audio_rows (the engine's last output, wherever the step wrote it), DUMP_ROWS objects at a time."""
+    rng = np.random.default_rng(DUMP_SEED)
+    ids = np.sort(rng.choice(n_obj, min(n_obj, DUMP_ROWS), replace=False))
+    rows = eng.audio_rows(ids)
+    row_len = rows.shape[1]
+    rows = np.ascontiguousarray(rows[:, :max(1, DUMP_ROW_FLOATS // len(ids))])
+    pos = np.sort(rng.choice(n_obj * row_len, min(DUMP_SAMPLES, n_obj * row_len), replace=False))
+    samples = np.empty(pos.size, dtype=np.float32)
+    bounds = np.searchsorted(pos, np.arange(0, n_obj + DUMP_ROWS, DUMP_ROWS) * row_len)
+    for k, a in enumerate(range(0, n_obj, DUMP_ROWS)):
+        lo, hi = bounds[k], bounds[k + 1]
+        if hi > lo:
+            chunk = eng.audio_rows(np.arange(a, min(n_obj, a + DUMP_ROWS))).reshape(-1)
+            samples[lo:hi] = chunk[pos[lo:hi] - a * row_len]
+    return {"audio_rows": rows, "audio_row_ids": ids.astype(np.float64), "audio_samples": samples}
+
+
+def write_dump(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def pmc_counts(form, objects, args):
@@ -697,6 +749,8 @@ def measure(args, ctx, global_ids, want_parity):
     if do_gather and not do_mix and backend == "nccl" and gathered is not None:
         last = (n_calls[0] - 1) % n_buf
         assert torch.equal(gathered[last][rank * cmax:rank * cmax + n_obj], audios[last][:n_obj])
+    # --dump-outputs: the last timed step's audio, read before anything below steps the engine again
+    dumped = last_step_sample(eng, n_obj) if ctx.get("dump_outputs") else None
 
     res = {
         "elapsed": elapsed, "n_local": n_obj, "n_hits": n_hits, "gather": bool(do_gather), "settle_steps": args.settle,
@@ -770,6 +824,7 @@ def measure(args, ctx, global_ids, want_parity):
             "pass": bool((mx <= TOL_MAX).all() and (l2 <= TOL_L2).all()),
         }
     res["_cpu_inputs"] = (lam, shapes, scripts)
+    res["dump"] = dumped
     res["device_group"] = bool(use_group)
     res["collective_by"] = ("pbso_group (C ABI: RCCL called from C++" + ("; ONE rank: the collectives are issued on a one-rank communicator, "
                             "nothing crosses a link)" if world == 1 else ")")) if use_group else (
@@ -852,30 +907,34 @@ def main():
     order = ["weak", "strong"] if args.weak and not args.strong else ["strong", "weak"]
     if world == 1:
         order = ["weak"]                               # one rank: the two legs are the same run
-    elif args.no_strong:
+    elif args.no_strong or not args.full:
         order = order[:1]
     legs = {}
     for leg in order:
         ids = weak_ids if leg == "weak" else strong_ids
         ctx["counts"] = [args.objects] * world if leg == "weak" else [hi - lo for lo, hi in spans]
-        ctx["measure_d2h"] = leg == order[0] and rank == 0
-        legs[leg] = measure(args, ctx, ids, want_parity=(not args.no_parity and leg == order[0] and rank == 0))
-        ctx["measure_d2h"] = False
+        ctx["measure_d2h"] = args.full and leg == order[0] and rank == 0
+        ctx["dump_outputs"] = bool(args.dump_outputs) and leg == order[0] and rank == 0
+        legs[leg] = measure(args, ctx, ids, want_parity=(args.full and not args.no_parity and leg == order[0] and rank == 0))
+        ctx["measure_d2h"] = ctx["dump_outputs"] = False
+        if legs[leg]["dump"] is not None:
+            write_dump(args.dump_outputs, legs[leg].pop("dump"))
     head = order[0]
     m = legs[head]
     # one GPU: the same workload once more in the OTHER block form, reported beside the headline
     second = second_form = None
-    if world == 1 and args.form in ("block", "block_bf16") and not args.no_second_form and args.scenario == "impulses":
+    if (args.full and world == 1 and args.form in ("block", "block_bf16") and not args.no_second_form
+            and args.scenario == "impulses"):
         import copy
         a2 = copy.copy(args)
         a2.form = second_form = "block_bf16" if args.form == "block" else "block"
         ctx["counts"] = [args.objects]
-        second = measure(a2, ctx, weak_ids, want_parity=(not args.no_parity and rank == 0))
+        second = measure(a2, ctx, weak_ids, want_parity=(args.full and not args.no_parity and rank == 0))
     # one GPU: the strong-scaling PROXY.  Objects are independent (modal_solver.h:100-126), so the per-rank compute of the
     # 2 / 4 / 8-GPU run of this configuration IS this GPU stepping objects / N of them: measured here, each with its own
     # oracle check, next to the efficiency it implies (this run's ms_per_step / N / the share's ms_per_step; the gather is extra)
     shares = []
-    if world == 1 and not args.no_strong_share and args.scenario == "impulses" and args.objects >= 16:
+    if args.full and world == 1 and not args.no_strong_share and args.scenario == "impulses" and args.objects >= 16:
         import copy
         for n_ranks in (2, 4, 8):
             if args.objects % n_ranks:
@@ -895,7 +954,7 @@ def main():
     # one GPU: the same scene stepped ONE SECOND of audio at a time (86 buffers per pbso_step: the step size of rounds 1 - 3 and of
     # SURVEY 8(d)'s parity runs) -- what a launch's fixed costs take when they are paid every second of audio instead of every ten
     one_second = None
-    if world == 1 and args.buffers > 86 and not args.no_one_second_leg and args.scenario == "impulses":
+    if args.full and world == 1 and args.buffers > 86 and not args.no_one_second_leg and args.scenario == "impulses":
         import copy
         a4 = copy.copy(args)
         a4.buffers = 86
@@ -915,7 +974,7 @@ def main():
     # what the collective costs: the head leg once more with the all-gather left out, with a gather to rank 0 only
     # (send / receive) and with the reduce a consumer of ONE mixed stream needs (reported beside it, never as `value`)
     bare = mixed = rooted = None
-    if m["gather"] and not args.no_gather_cost:
+    if args.full and m["gather"] and not args.no_gather_cost:
         cnt = [args.objects] * world if head == "weak" else [hi - lo for lo, hi in spans]
         ids = weak_ids if head == "weak" else strong_ids
         ctx["counts"] = cnt
@@ -1208,7 +1267,7 @@ def main():
                 out[leg] = dict(leg_numbers(leg, r), scaling=leg,
                                 note="--objects objects (the configuration as written) split over the ranks by the sum of modes"
                                 if leg == "strong" else "--objects per GPU")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, *m["_cpu_inputs"])
             except Exception as ex:   # the baseline must never take the GPU number down with it

@@ -8,8 +8,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out/p6; export TMPDIR=/tmp;
 WHAT="${1:-tests bench stats pmc}"
 if [[ $WHAT == *tests* ]]; then timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -4 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt; fi
 if [[ $WHAT == *bench* ]]; then
-  t0=$(date +%s); python bench.py > $O/bench_default.json 2> $O/bench_default.err; t1=$(date +%s); echo "python bench.py: $((t1 - t0)) s wall" | tee $O/default_command_wall_seconds.txt
-  python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags_steps20_warmup5.json 2> /dev/null
+  t0=$(date +%s); python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; t1=$(date +%s); echo "python bench.py --full: $((t1 - t0)) s wall" | tee $O/default_command_wall_seconds.txt
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags_steps20_warmup5.json 2> /dev/null
 fi
 if [[ $WHAT == *stats* ]]; then
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_default -- python3 $R/bench.py --no-cpu-baseline --no-second-form --no-one-second-leg > $O/st_default.log 2>&1)

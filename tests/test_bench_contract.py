@@ -124,3 +124,41 @@ def test_bench_defaults_are_the_single_gpu_headline(monkeypatch):
     for o, m, nb in ((1, 512, 86), (64, 256, 86), (8, 4096, 860), (4096, 64, 1)):
         assert bench.auto_settle(o, m, nb) * nb >= 3000                        # never fewer than the 40 s of audio of rounds 1 - 4
     assert bench.parse(["--settle", "3"]).settle == 3 and not bench.parse(["--settle", "3"]).settle_auto
+
+
+def test_plain_run_is_the_headline_only_and_full_is_opt_in():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+
+
+def test_dumped_sample_is_fixed_bounded_and_taken_from_the_last_step():
+    """bench.last_step_sample against a stand-in engine whose last step is a known array: whole rows of some objects and
+    single samples over all of them, float32 / float64 only, at most 64 MB, the same every time"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+
+    class Eng:
+        def __init__(self, audio):
+            self.audio = audio
+
+        def audio_rows(self, rows):
+            return self.audio[np.asarray(rows)]
+
+    for n_obj, row_len in ((1, 513), (100, 86 * 513), (40, 4000 * 513)):
+        audio = np.random.default_rng(n_obj).standard_normal((n_obj, row_len)).astype(np.float32)
+        d = bench.last_step_sample(Eng(audio), n_obj)
+        assert set(d) == {"audio_rows", "audio_row_ids", "audio_samples"}
+        assert all(x.dtype in (np.float32, np.float64) for x in d.values())
+        assert sum(x.nbytes for x in d.values()) <= 64 << 20
+        ids = d["audio_row_ids"].astype(int)
+        assert ids.size == min(n_obj, bench.DUMP_ROWS) and np.unique(ids).size == ids.size
+        assert np.array_equal(d["audio_rows"], audio[ids, :d["audio_rows"].shape[1]])
+        assert d["audio_samples"].size == min(bench.DUMP_SAMPLES, audio.size)
+        assert np.isin(d["audio_samples"], audio).all()
+        again = bench.last_step_sample(Eng(audio.copy()), n_obj)
+        assert all(np.array_equal(d[k], again[k]) for k in d)

@@ -18,7 +18,7 @@ def test_two_ranks_on_one_gpu_print_one_line_with_gather_and_strong_leg():
     env = dict(os.environ, PBSO_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--objects", "96", "--buffers", "86", "--steps", "3", "--warmup", "1",
-                        "--settle", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+                        "--settle", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout                     # ONE JSON line, from rank 0
@@ -59,7 +59,7 @@ def test_one_rank_under_torchrun_issues_the_groups_collectives_on_a_one_rank_com
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--objects", "256", "--steps", "8",
-                        "--warmup", "2", "--settle", "4", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+                        "--warmup", "2", "--settle", "4", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
