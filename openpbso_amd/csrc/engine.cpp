@@ -402,16 +402,14 @@ int Engine::init() {
             return fail(PBSO_ERR_HIP, "stream_sync = 4: no pinned host memory for the gate's word");
         gate_choice_ = desc_.stream_sync == 4 ? 2 : start_gate_ ? 1 : 0;
     }
+    // (waited for by the engine's own streams only, never by the host or another device: without the system-scope fence
+    //  a record costs the stream nothing -- 4 us with it, scripts/microbench/wait_value.hip; +0.4 % per step at 1024 x 512)
+    constexpr unsigned device_event_flags = hipEventDisableTiming | hipEventDisableSystemFence;
     for (int i = 0; i < N_SETS; ++i) {
-        // (waited for by the engine's own streams only, never by the host or another device: without the system-scope fence
-        //  a record costs the stream nothing -- 4 us with it, scripts/microbench/wait_value.hip; +0.4 % per step at 1024 x 512)
-#ifndef PBSO_DEVICE_EVENT_FLAGS
-#define PBSO_DEVICE_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
-#endif
-        HIPTRY(hipEventCreateWithFlags(&ev_prep_done_[i], PBSO_DEVICE_EVENT_FLAGS));
-        HIPTRY(hipEventCreateWithFlags(&ev_k1_done_[i], PBSO_DEVICE_EVENT_FLAGS));
-        HIPTRY(hipEventCreateWithFlags(&ev_aux_fork_[i], PBSO_DEVICE_EVENT_FLAGS));
-        HIPTRY(hipEventCreateWithFlags(&ev_aux_join_[i], PBSO_DEVICE_EVENT_FLAGS));
+        HIPTRY(hipEventCreateWithFlags(&ev_prep_done_[i], device_event_flags));
+        HIPTRY(hipEventCreateWithFlags(&ev_k1_done_[i], device_event_flags));
+        HIPTRY(hipEventCreateWithFlags(&ev_aux_fork_[i], device_event_flags));
+        HIPTRY(hipEventCreateWithFlags(&ev_aux_join_[i], device_event_flags));
     }
     plan_threads_ = std::min(16, std::max(1, desc_.plan_threads));
     ctx_.resize(plan_threads_);
@@ -1116,10 +1114,7 @@ int Engine::warm_copy_engines() {
     if (desc_.warm_copies < 0) return PBSO_OK;
     // Best effort: a failure here costs a slow first launch, never the engine (errors are swallowed, everything is released).
     // A caller's stream is not touched: the second pattern only needs SOME stream the preparation stream waits for.
-#ifndef PBSO_WARM_CHUNK_MB
-#define PBSO_WARM_CHUNK_MB 1
-#endif
-    const size_t chunk = (size_t)PBSO_WARM_CHUNK_MB << 20;
+    constexpr size_t chunk = (size_t)1 << 20;
     const int n = 6;
     PinBuf<unsigned char> h;
     DevBuf<unsigned char> d;
@@ -2678,7 +2673,6 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
     if (tc_launch) {
         TcSet &ts = tc_[tc_set];
         kp.tc_cb = tc_cb;
-        if (const char *v = std::getenv("PBSO_TC_LDS_PAD")) kp.lds_pad = std::atoi(v);      // (diagnostics: scripts/debug/r06_c5_occupancy.sh)
         kp.tc_xs = d_xs_[cur_set_].p;
         kp.tc_xtrow = d_xtrow_[cur_set_].p;
         kp.census_stride = ts.n_teams;

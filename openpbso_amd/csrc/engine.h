@@ -276,10 +276,7 @@ private:
     // and then) is absorbed by the steps already queued instead of idling the device.  Not four: with three steps of preparation
     // kernels queued ahead, the 64 x 256 scene with a listener move per buffer loses the overlap between its steps (0.24 -> 0.36 ms
     // per step, scripts/debug/r03_sets.sh; the headline and the scraping scene do not care).
-#ifndef PBSO_N_SETS
-#define PBSO_N_SETS 3
-#endif
-    static constexpr int N_SETS = PBSO_N_SETS;
+    static constexpr int N_SETS = 3;
     hipEvent_t ev_prep_done_[N_SETS] = {}, ev_k1_done_[N_SETS] = {};
     hipEvent_t ev_aux_fork_[N_SETS] = {}, ev_aux_join_[N_SETS] = {};      // the preparation's fork to aux_stream_ and its way back
     // engines with several team sizes: the size classes are launched side by side on these streams
@@ -444,7 +441,7 @@ private:
     bool fuse_short_ = true;                             // pbso_engine_desc::fuse_short_launches
     // the second submitting thread (submit_queue.h; pbso_engine_desc::submit_thread): created by finalize, nullptr = every call at once
     SubmitQueue *submit_ = nullptr;
-    unsigned long long set_batch_[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // per plan set: the batch of the launch that last used it
+    unsigned long long set_batch_[N_SETS] = {};          // per plan set: the batch of the launch that last used it
     std::vector<ArStream> ar_streams_;
     std::vector<ArUse> ar_uses_;
     std::vector<int> seg_stream_, ar_stream_of_state_, ar_last_use_, ar_epoch_, ar_param_;

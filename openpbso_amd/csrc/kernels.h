@@ -5,18 +5,6 @@
 
 namespace pbso {
 
-// Wave priority of the preparation's kernels (profiles, projection, combine, increments, scan): they are small, they run BESIDE the
-// oscillator bank, and the next bank waits for them (build option for A/B runs: scripts/debug/r05_prep_prio.sh)
-#ifndef PBSO_PREP_PRIO
-#define PBSO_PREP_PRIO 0
-#endif
-#if defined(__HIPCC__)
-__device__ __forceinline__ void prep_prio() {
-    if (PBSO_PREP_PRIO > 0) __builtin_amdgcn_s_setprio(PBSO_PREP_PRIO);
-}
-#endif
-
-
 // one audio buffer is processed as tiles of TILE samples; 513 = 19 * 27.
 // 27 rows x 68 floats = 7.3 KB of LDS per wave: 16+ waves per CU fit, which the
 // VALU issue rate needs (one wave alone issues a v_fma_f32 every ~5.5 cycles,
@@ -27,12 +15,7 @@ constexpr int TILE = 27;
 // group on 16 distinct 4-bank slots (68 mod 64 = 4).
 constexpr int LDS_ROW = 68;
 constexpr int MAX_TILES = 32;          // tile mask is 32 bits
-#ifdef PBSO_WAVE_TRACE
-constexpr int TRACE_B0 = 40, TRACE_NB = 12, TRACE_K = 8;          // K1b diagnostics build: per-wave stamps of buffers 40 .. 51 behind the row
-constexpr int CENSUS_WORDS = 12 + 2 * (2 + TRACE_NB * TRACE_K);
-#else
 constexpr int CENSUS_WORDS = 12;       // diagnostics row per workgroup (PBSO_CENSUS=1)
-#endif
 
 // transfer-row codes in BufDesc::trow
 constexpr int XFER_KEEP = -1;          // keep _latest_transfer
@@ -113,7 +96,6 @@ struct IirParams {
     // time-chunked launch of the block form (kernels_scan.hip): tc_cb > 0 buffers per chunk, grid (team, chunk); the states at
     // the chunks' first buffers [n_obj][n_chunks][m_pad] pairs (q, d), unscaled, and the transfer rows in force there
     int tc_cb = 0;
-    int lds_pad = 0;             // diagnostics (PBSO_TC_LDS_PAD): extra dynamic LDS per workgroup of a time-chunked block launch -- fewer teams per CU
     const float *tc_xs = nullptr;
     const int *tc_xtrow = nullptr;
     int census_stride = 0;       // census rows per chunk (= the launch's teams, all size classes)

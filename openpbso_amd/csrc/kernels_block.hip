@@ -114,14 +114,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // The samples leave the kernel for good (181 MB per launch at 1024 x 512 x 86): nontemporal stores keep them from pushing the
 // operand tables and coefficient rows out of the L2 (kernel 0.944 -> 0.939 ms; write-through `sc0 sc1` stores: 0.954;
-// scripts/debug/r04_nt.sh).  -DPBSO_AUDIO_STORE=0: plain stores, 2: write-through.
-#if defined(PBSO_AUDIO_STORE) && PBSO_AUDIO_STORE == 0
-#define AUDIO_STORE(p, v) (*(p) = (v))
-#elif defined(PBSO_AUDIO_STORE) && PBSO_AUDIO_STORE == 2
-#define AUDIO_STORE(p, v) asm volatile("global_store_dword %0, %1, off sc0 sc1" :: "v"(p), "v"(v) : "memory")
-#else
+// scripts/debug/r04_nt.sh).
 #define AUDIO_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#endif
 
 template <int K0, int N, class F>
 __device__ __forceinline__ void static_for(F &&f) {
@@ -225,11 +219,7 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
 #pragma unroll
             for (int i = 0; i < 8; ++i)
 #pragma unroll
-#ifdef PBSO_ABL_W_COALESCED        // (ablation, wrong results: what the permuted read of the table costs a time-chunked launch's preamble)
-                for (int jj = 0; jj < 4; ++jj) wreg4[r][i][jj] = wsrc[(4 * i + jj) * 64 + lane];
-#else
                 for (int jj = 0; jj < 4; ++jj) wreg4[r][i][jj] = wsrc[(8 * (lane >> 4) + i) * 64 + 16 * jj + (lane & 15)];
-#endif
         } else {
             const unsigned *__restrict__ wu = reinterpret_cast<const unsigned *>(wsrc);
 #pragma unroll
@@ -484,12 +474,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                      : "memory");
     };
 #undef PBSO_PK_PAIR
-#ifndef PBSO_VB_FORM
-#define PBSO_VB_FORM 1           // 1: vburst_pk; 0: the four-instruction steps (A/B builds)
-#endif
-#ifndef PBSO_REFILL
-#define PBSO_REFILL 0            // 0: one ds_read_b128 behind every fourth MFMA; 1: all eight behind the burst's last MFMA (A/B builds)
-#endif
     auto coarse2 = [&](int r, auto nc, int blk) {
         constexpr int n = decltype(nc)::value;         // even
         static_assert((n & 1) == 0 && park_off(n + 1) - park_off(n) == ST_PAIR, "a pair of blocks = two rows of the image");
@@ -504,27 +488,11 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
 
     // diagnostics (PBSO_CENSUS=1): where wave 0's shader cycles go
     unsigned long long cy_head = 0, cy_pipe = 0, cy_bar = 0, cy_comb = 0, cy_mark = 0, cy_taps = 0, cy_step = 0;
-#ifdef PBSO_WAVE_TRACE
-    // diagnostics build (scripts/debug/r06_wave_trace.py): EVERY wave of a team of <= 2 keeps the shader-clock times at which it
-    // left the head, the pipeline, the barrier and the combine of TRACE_NB buffers in the middle of the launch, and its HW_ID:
-    // do the two waves of a SIMD (they belong to different teams) take their heads together or one under the other's pipeline?
-    int trace_b = -1;
-    unsigned long long *trace_row = (p_census && wave < 2)
-        ? p_census + ((size_t)team.id + (size_t)chunk * p.census_stride) * CENSUS_WORDS + 12 + wave * (2 + TRACE_NB * TRACE_K) : nullptr;
-    if (trace_row && lane == 0) {
-        trace_row[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-        trace_row[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    }
-#endif
-    auto lap = [&](unsigned long long &acc, int k = -1) {
+    auto lap = [&](unsigned long long &acc) {
         if (p_census) {
             const unsigned long long now = __builtin_amdgcn_s_memtime();
             acc += now - cy_mark;
             cy_mark = now;
-#ifdef PBSO_WAVE_TRACE
-            if (trace_row && k >= 0 && trace_b >= TRACE_B0 && trace_b < TRACE_B0 + TRACE_NB && lane == 0)
-                trace_row[2 + (trace_b - TRACE_B0) * TRACE_K + k] = now;
-#endif
         }
     };
     BufDesc next = dsc[b_begin];
@@ -544,33 +512,25 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
         prio_rank = (int)(__builtin_bit_cast(unsigned, lds[ST_FLOATS]) & 3u);       // wave 0's ring[0]
         __syncthreads();
         // (starting the teams of a CU half a slice period apart -- one wave's vector burst under its SIMD partner's matrix
-        //  burst -- changed nothing: 0.948 ms with any stagger of 1, 2 or 4 K cycles on either rank bit, 0.948 without)
-#ifdef PBSO_STAGGER_BIT
-        // (round 5, scripts/debug/r05_stagger.sh: half a BUFFER apart -- one team's head and combine under its SIMD partner's
+        //  burst -- changed nothing: 0.948 ms with any stagger of 1, 2 or 4 K cycles on either rank bit, 0.948 without;
+        //  round 5, scripts/debug/r05_stagger.sh: half a BUFFER apart -- one team's head and combine under its SIMD partner's
         //  pipeline -- 8 or 16 K cycles on rank bit 1 or 2: 9.147 / 9.148 / 9.257 / 9.276 ms per 860 buffers against 9.18 - 9.27
-        //  of the product on the same box: nothing either; kept as a build option for the next idea)
-        if (prio_rank & PBSO_STAGGER_BIT)
-            for (int i = 0; i < PBSO_STAGGER_N; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
+        //  of the product on the same box: nothing either)
     }
     for (int b = b_begin; b < b_end; ++b) {
         const BufDesc cur = next;
         next = dsc[b + 1 < p.nb ? b + 1 : b];
-#ifndef PBSO_HPRIO
-#define PBSO_HPRIO 0             // A/B builds: 1 = a wave outside its pipeline (head, barrier, combine) runs at priority 3, its pipeline at 0 .. 2 in rotation
-#endif
         auto set_pipe_prio = [&]() {
             if (p.rotate) {
                 switch ((prio_rank + b - b_begin) & 3) {       // (the team's OWN buffer count: the chunks of a CU start together at different b)
                 case 0: __builtin_amdgcn_s_setprio(0); break;
                 case 1: __builtin_amdgcn_s_setprio(1); break;
                 case 2: __builtin_amdgcn_s_setprio(2); break;
-                default: __builtin_amdgcn_s_setprio(PBSO_HPRIO ? 1 : 3); break;
+                default: __builtin_amdgcn_s_setprio(3); break;
                 }
             }
         };
-        if (PBSO_HPRIO) { if (p.rotate) __builtin_amdgcn_s_setprio(3); }
-        else set_pipe_prio();
+        set_pipe_prio();                               // (a lambda: written inline, the compiler swaps two s_mov in the loop's preheader)
 
         const int frow = cur.frow;
         const int prow = (cur.flags & DESC_DIRECT) ? -1 : cur.prow;     // (a direct hit keeps its normal there)
@@ -609,9 +569,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
             }
         };
         dump_b = p.qn_b0 + b;
-#ifdef PBSO_WAVE_TRACE
-        trace_b = b - b_begin;
-#endif
 
         if (flags & DESC_SKIP) {
             dump_scale(-1);
@@ -652,9 +609,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
             g_[r] = frow >= 0 ? (scaled ? gv * t[r] : gv) : 0.f;
         }
         prefetch_direct(next);                             // (the landing area is free again: the dot above has read it)
-#ifdef PBSO_WAVE_TRACE
-        lap(cy_head, 4);
-#endif
         const bool impulse = (flags & DESC_IMPULSE) != 0;
         const bool dense = frow >= 0 && !impulse;
 
@@ -674,9 +628,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                 x2[v].x = x2[v].x + a;
                 p0 = (v == 0) ? x2[v].x : p0 + x2[v].x;
             }
-#ifdef PBSO_WAVE_TRACE
-            lap(cy_head, 5);
-#endif
             if (QN) {
                 // sum_{k=0}^{B-1} q_k^2 = x0' G x0, x0 = state after sample 0 (the rest of the buffer is force-free)
                 const unsigned utid = lane_off();
@@ -690,9 +641,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                     (b_qn + (size_t)b * p.m_pad)[v * rowlen + utid] = nrm * __builtin_amdgcn_rcpf(t[v]);
                 }
             }
-#ifdef PBSO_WAVE_TRACE
-            lap(cy_head, 6);
-#endif
             p0 = wave_sum(p0);
             if (lane == 0) *ring_s0() = p0;
 
@@ -708,24 +656,13 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
             // between every two MFMAs each of the two waves of a SIMD paid that wait 16 times per slice; in bursts the
             // partner's vector burst runs under this wave's matrix burst.
             f4 bq[8];                                  // the slice's 32 B operands: MFMA s takes bq[s >> 2][s & 3]
-            lap(cy_head, 0);
-            if (PBSO_HPRIO) set_pipe_prio();
-#ifdef PBSO_ABL_PIPE_REPEAT
-            // ablation (wrong results on purpose, scripts/debug/r06_ablate.sh): the pipeline of a buffer runs N times -- what one more
-            // pass costs is the pipeline's own pace, the rest of the kernel's time is what sits around it
-            int abl_reps = PBSO_ABL_PIPE_REPEAT;
-            asm volatile("" : "+s"(abl_reps));
-            for (int abl_rep = 0; abl_rep < abl_reps; ++abl_rep) {
-#endif
+            lap(cy_head);
             wave_sync();                               // the previous buffer's staging reads are issued
-            if constexpr (!DUMP && PBSO_VB_FORM == 1) vburst_pk(0);
+            if constexpr (!DUMP) vburst_pk(0);
             else static_for<0, BN / 2>([&](auto hc) { coarse2(0, std::integral_constant<int, 2 * decltype(hc)::value>{}, 2 * decltype(hc)::value); });
             wave_sync();
 #pragma unroll
             for (int i = 0; i < 8; ++i) bq[i] = bsrc[i];
-#ifdef PBSO_WAVE_TRACE
-            lap(cy_pipe, 7);
-#endif
             f4 acc0, acc1;
             static_for<0, U>([&](auto uc) {
                 constexpr int u = decltype(uc)::value;
@@ -739,7 +676,7 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                 wave_sync();                           // this slice's operand reads are issued: the staging area is free
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (more) {
-                    if constexpr (!DUMP && PBSO_VB_FORM == 1) vburst_pk(rn);
+                    if constexpr (!DUMP) vburst_pk(rn);
                     else static_for<0, BN / 2>([&](auto hc) {
                         constexpr int n = 2 * decltype(hc)::value;
                         coarse2(rn, std::integral_constant<int, n>{}, BN * ((u + 1) / R) + n);
@@ -747,43 +684,21 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                     wave_sync();
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef PBSO_MB_PRIO
-                __builtin_amdgcn_s_setprio(PBSO_MB_PRIO);          // (A/B: the matrix burst above / below the partner's vector instructions)
-#endif
                 static_for<0, 32>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     if constexpr (s & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg4[r][s >> 2][s & 3], bq[s >> 2][s & 3], acc1, 0, 0, 0);
                     else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg4[r][s >> 2][s & 3], bq[s >> 2][s & 3], acc0, 0, 0, 0);
                     // refill: one ds_read_b128 behind every fourth MFMA, for the four operands consumed BEFORE these (the MFMA reads its
-                    // operands in its first pass).  A/B builds: PBSO_REFILL == 2 refills the four just consumed, 1 issues all eight
-                    // behind the burst's last MFMA (kernel 9.03 ms per 860 buffers against 8.83: scripts/debug/r06_ablate.sh)
-                    if constexpr (PBSO_REFILL == 0 && more && (s & 3) == 3 && s >= 7) bq[(s >> 2) - 1] = bsrc[(s >> 2) - 1];
-                    if constexpr (PBSO_REFILL == 2 && more && (s & 3) == 3) bq[s >> 2] = bsrc[s >> 2];
-                    if constexpr (PBSO_REFILL == 3 && more && (s & 7) == 7 && s >= 15) {      // (two reads behind every eighth MFMA)
-                        bq[(s >> 2) - 3] = bsrc[(s >> 2) - 3];
-                        bq[(s >> 2) - 2] = bsrc[(s >> 2) - 2];
-                    }
+                    // operands in its first pass).  Measured and removed (scripts/debug/r06_ablate.sh): all eight behind the burst's last
+                    // MFMA, kernel 9.03 ms per 860 buffers against 8.83; the read refilling the four just consumed: the same
+                    if constexpr (more && (s & 3) == 3 && s >= 7) bq[(s >> 2) - 1] = bsrc[(s >> 2) - 1];
                     // last slice: nothing to refill -- half way through the burst the first operand registers are free and the
                     // next buffer's inputs land in them
                     if constexpr (!more && s == 15) prefetch(next, false);
-#ifndef PBSO_NO_MB_SCHED_BARRIER
                     __builtin_amdgcn_sched_barrier(0);
-#endif
                 });
-#ifdef PBSO_MB_PRIO
-                __builtin_amdgcn_s_setprio(PBSO_MB_PRIO_VB);
-#endif
-                if constexpr (more) {
-                    if constexpr (PBSO_REFILL == 0) bq[7] = bsrc[7];
-                    else if constexpr (PBSO_REFILL == 3) { bq[6] = bsrc[6]; bq[7] = bsrc[7]; }
-                    else if constexpr (PBSO_REFILL == 1) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) bq[i] = bsrc[i];
-                    }
-                } else {
-                    prefetch_gq();
-                    if (PBSO_HPRIO && p.rotate) __builtin_amdgcn_s_setprio(3);
-                }
+                if constexpr (more) bq[7] = bsrc[7];
+                else prefetch_gq();
                 if constexpr (r == R - 1) {
                     const f4 acc = acc0 + acc1;
                     const unsigned l = lane_off() & 63u;       // (recomputed: not worth two registers across the pipeline)
@@ -791,9 +706,6 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                     combine_half(grp);
                 }
             });
-#ifdef PBSO_ABL_PIPE_REPEAT
-            }
-#endif
             } else {
                 // ---- split-bf16 projection.  The lane that owns a mode parks every block-start state twice: hi =
                 // the top 8 significant bits of x (rounded) and lo = the next 8 of x - hi, both bf16 bit patterns; the
@@ -1231,14 +1143,10 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
 
         // ---- the team's waves add their rings and store the buffer; one barrier per buffer (the ring
         //      alternates by buffer parity, so a wave can be one buffer ahead of the slowest reader)
-#ifdef PBSO_ABL_NO_COMBINE
-        if constexpr (false) {             // ablation: no barrier, no ring sums, no sample stores
-#else
         if constexpr (!HALF) {
-#endif
-        lap(cy_pipe, 1);
+        lap(cy_pipe);
         __syncthreads();
-        lap(cy_bar, 2);
+        lap(cy_bar);
         {
             // thread j adds the waves' ring entries 4j .. 4j+3 (samples 4j+1 .. 4j+4); thread 0 also sample 0
             const float *r0 = lds + ST_FLOATS + (b & 1) * RING;
@@ -1259,7 +1167,7 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                 AUDIO_STORE(&ao[0], acc);
             }
         }
-        lap(cy_comb, 3);
+        lap(cy_comb);
         }
     }
 
@@ -1296,7 +1204,7 @@ static int launch_one(const IirParams &p, int n_teams, int W, hipStream_t stream
         if (p.tc_cb > 0) return launch_one<R, QNM, PROJ, DUMP, FORCED, true>(p, n_teams, W, stream);
     }
     if (!CHUNKED && p.tc_cb > 0) return (int)hipErrorInvalidValue;       // (no chunked build of this shape: the engine never asks)
-    const size_t lds = block_lds_bytes(W, R) + (CHUNKED ? (size_t)p.lds_pad : 0);
+    const size_t lds = block_lds_bytes(W, R);
     constexpr int MAXT = 64 * MAX_WAVES_PER_BLOCK_TEAM;
     if (64 * W > MAXT) return (int)hipErrorInvalidValue;
     auto kern = iir_block_kernel<R, QNM, PROJ, DUMP, MAXT, FORCED, CHUNKED>;
@@ -1327,7 +1235,7 @@ static int launch_r(const IirParams &p, int n_teams, int W, bool qn, int proj, h
 
 // The builds of one, two and four modes per lane are TWO translation units (the Makefile compiles this file twice, in parallel:
 // -DPBSO_BLOCK_PART=0 the four-modes-per-lane builds + everything else in this file, =1 the builds of one and two); without the
-// macro -- tests/test_kernel_asm_guards.py, the A/B variants of scripts/debug/r06_variant.sh with -DPBSO_ONLY_R4 -- one unit.
+// macro -- tests/test_kernel_asm_guards.py, with -DPBSO_ONLY_R4 -- one unit.
 int launch_block_r1(const IirParams &p, int n_teams, int W, bool qn, int proj, hipStream_t s);
 int launch_block_r2(const IirParams &p, int n_teams, int W, bool qn, int proj, hipStream_t s);
 #if !defined(PBSO_ONLY_R4) && (!defined(PBSO_BLOCK_PART) || PBSO_BLOCK_PART == 1)

@@ -59,7 +59,6 @@ __global__ __launch_bounds__(256) void modal_project_kernel(
     const ProjectEvent *__restrict__ events, const double *__restrict__ shapes,
     const long long *__restrict__ shape_off, const int *__restrict__ n_modes,
     double *__restrict__ slots, int m_pad) {
-    prep_prio();
     const RowTile rt = row_tile(m_pad);
     const ProjectEvent ev = events[rt.row];
     const int m = rt.tile * blockDim.x + threadIdx.x;
@@ -146,7 +145,6 @@ __global__ __launch_bounds__(256) void force_combine_kernel(
     const double *__restrict__ c3, float *__restrict__ grows, const ProjectEvent *__restrict__ direct,
     const double *__restrict__ shapes, const long long *__restrict__ shape_off, const int *__restrict__ n_modes,
     int m_pad, int n_events, const double *__restrict__ stage, const int *__restrict__ stage_slot, double *slots_w) {
-    prep_prio();
     force_combine_body(blockIdx.x, row_ptr, slot_idx, row_obj, slots, c3, grows, direct, shapes, shape_off, n_modes, m_pad, n_events, stage,
                        stage_slot, slots_w);
 }
@@ -293,10 +291,6 @@ __global__ __launch_bounds__(K2_THREADS) void force_profile_kernel(
                 __syncthreads();
                 uint32_t xb = s.x;                                              // state before candidate K2_THREADS k
                 int acc_pairs = 0;
-#ifdef PBSO_K2_ABLATE_RNG
-                acc_pairs = pairs_needed;
-                for (int i = lane; i < frames; i += K2_THREADS) nrm[i] = 0.25;
-#endif
                 for (int batch = 0; acc_pairs < pairs_needed; ++batch) {
                     uint32_t st = mulmod31(xb, pj);                             // state before candidate K2_THREADS k + lane
                     const uint32_t d1 = (st = mulmod31(st, 16807u));
@@ -350,11 +344,7 @@ __global__ __launch_bounds__(K2_THREADS) void force_profile_kernel(
                 // critical path (LDS latency and the _buf index arithmetic are off it).
                 for (int ii = lane; ii < frames; ii += K2_THREADS) nrm[ii] = s.sigma * nrm[ii];
                 __syncthreads();
-#ifdef PBSO_K2_ABLATE_SCAN
-                if (false) {
-#else
                 if (!ar_serial && wv == 0) {
-#endif
                     // ---- AR(2) as a parallel scan (the default).  x_k = a0 x_{k-1} + a1 x_{k-2} + c_k is linear with
                     // constant coefficients within a row: lane l of wave 0 runs the recurrence over its L consecutive
                     // samples from a zero state (lane 0: from the force's history), a Kogge-Stone scan over the lanes
@@ -633,7 +623,6 @@ __device__ __forceinline__ void ar_variates_body(
 __global__ __launch_bounds__(K2_THREADS) void ar_variates_kernel(
     const int *__restrict__ seg_stream, const ArStream *__restrict__ streams, const ArState *__restrict__ states,
     ArState *__restrict__ snaps, double *__restrict__ vnorm, uint32_t *__restrict__ vstate, int *__restrict__ seg_count) {
-    prep_prio();
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     ar_variates_body((int)blockIdx.x, seg_stream[blockIdx.x], cnt, streams, states, snaps, vnorm, vstate, seg_count);
 }
@@ -828,7 +817,6 @@ __global__ __launch_bounds__(K2_THREADS) void ar_zero_state_kernel(
     const ArState *__restrict__ snaps, const double *__restrict__ vnorm, const uint32_t *__restrict__ vstate,
     const int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs, ArFin *__restrict__ fins,
     int frames, int c_pitch) {
-    prep_prio();
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     __shared__ int carry;
@@ -911,7 +899,6 @@ __global__ __launch_bounds__(K2_THREADS) void force_rows_kernel(
     const ArStream *__restrict__ streams, const ArState *__restrict__ snaps, const ArRec *__restrict__ recs,
     const ArFin *__restrict__ fins, const double *__restrict__ cbuf, ArState *__restrict__ states, float *__restrict__ tprof,
     int frames, int b_pad, int c_pitch) {
-    prep_prio();
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     force_rows_body((int)blockIdx.x, k2_lds, rows, entries, uses, streams, snaps, recs, fins, cbuf, states, tprof, frames, b_pad, c_pitch);
 }
@@ -951,7 +938,6 @@ __global__ __launch_bounds__(K2_THREADS) void force_rows_fused_kernel(
     const ArStream *__restrict__ streams, ArState *__restrict__ states, ArState *__restrict__ snaps, double *__restrict__ vnorm,
     uint32_t *__restrict__ vstate, int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs,
     ArFin *__restrict__ fins, float *__restrict__ tprof, int frames, int b_pad, int c_pitch) {
-    prep_prio();
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     __shared__ int carry;
@@ -982,7 +968,6 @@ __global__ __launch_bounds__(K2_THREADS) void force_rows_combine_kernel(
     const ArStream *__restrict__ streams, ArState *__restrict__ states, ArState *__restrict__ snaps, double *__restrict__ vnorm,
     uint32_t *__restrict__ vstate, int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs,
     ArFin *__restrict__ fins, float *__restrict__ tprof, int frames, int b_pad, int c_pitch, CombineArgs c) {
-    prep_prio();
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     __shared__ int carry;

@@ -610,7 +610,9 @@ __global__ __launch_bounds__(640) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // scripts/debug/r05_pipe5_placement.py); in the order P0 A0 B0 C0 | P1 A1 B1 C1 | D0 D1 both P -- light, latency-bound -- share
     // their SIMD with ONE matrix wave.  The matrix work then sits 32 | 104 | 72 | 64 MFMAs per buffer on the four SIMDs and the second
     // one paces the kernel (5.2 K cycles per buffer); P0 C0 A1 B1 | P1 D0 B0 C1 | A0 D1 -- 36 | 96 | 72 | 68 -- was slower (5.6 K: the
-    // increment waves carry more than their MFMAs).  An even split needs finer roles than one group per wave: not built.
+    // increment waves carry more than their MFMAs).  The order below, P0 P1 B0 B1 | A1 A0 C0 C1 | D1 D0, gives every SIMD two matrix
+    // waves (A + D = B + C = 68 MFMAs) with the P on top of two of them: 5.0 K cycles per buffer.  An even split needs finer roles than
+    // one group per wave: not built.
     __shared__ __attribute__((aligned(16))) float lds_stage_[2][2][2][ST5_AREA];  // [slice][buffer parity][group]: parked t x
     __shared__ __attribute__((aligned(16))) float lds_u_[2][2][64 * U_ROW];       // [slice][group]: the increments of the buffer P steps next
     __shared__ f2 lds_raw_[2][QN ? 2 : 1][8][64];    // [slice][parity][every fourth block]: the unweighted state (unscaled buffers' qnorm chains)
@@ -620,17 +622,9 @@ __global__ __launch_bounds__(640) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __shared__ __attribute__((aligned(16))) float lds_t_[2][QN ? 4 : 1][2 * GROUP];   // [slice][buffer & 3]: T_1 .. T_512 for the qnorm chains
     __shared__ int lds_flag_[2];                     // buffers whose increments P has taken into registers
     const int wave_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifndef PBSO_PIPE5_ORDER
-#define PBSO_PIPE5_ORDER 2
-#endif
-#if PBSO_PIPE5_ORDER == 1        // P0 A0 B0 C0 | P1 A1 B1 C1 | D0 D1
-    const int slice = wave_wg < 8 ? wave_wg >> 2 : wave_wg - 8;
-    const int wave = wave_wg < 8 ? (wave_wg & 3) : 4;                             // the role: 0 P, 1 A, 2 B, 3 C, 4 D
-#else                            // P0 P1 B0 B1 | A1 A0 C0 C1 | D1 D0: every SIMD two matrix waves (A + D = B + C = 68 MFMAs), the P on top
-    //                                  w:  0  1  2  3  4  5  6  7  8  9
+    // the slice and the role (0 P, 1 A, 2 B, 3 C, 4 D) of wave w:  0  1  2  3  4  5  6  7  8  9
     const int slice = (0x19Au >> wave_wg) & 1;                                    // 0  1  0  1  1  0  0  1  1  0
     const int wave = (int)((0x4433112200ull >> (4 * wave_wg)) & 15);             // 0  0  2  2  1  1  3  3  4  4
-#endif
     float (*lds_stage)[2][ST5_AREA] = lds_stage_[slice];
     float (*lds_u)[64 * U_ROW] = lds_u_[slice];
     f2 (*lds_raw)[8][64] = lds_raw_[slice];

@@ -69,10 +69,6 @@ struct ScanDims {
     long long plane;             // elements between the planes of p_sc / p_pc
 };
 
-#ifndef PBSO_SCAN_STOP
-#define PBSO_SCAN_STOP 9         // (ablation builds for timing only: scripts/debug/r04_scan_abl.sh)
-#endif
-
 // One body, two kernels.  SERIAL (iir_scan_kernel): one wave per 64 columns of an object walks ALL buffers of the launch, batches
 // of 64, and stores the state at every chunk start.  SEG (iir_scan_seg_kernel, round 5): the scan cut along the time axis itself.
 // A chunk of buffers is an AFFINE map of the state,
@@ -279,9 +275,9 @@ __device__ __forceinline__ void scan_body(
     float r[HB][NR];
     f2 vv[DENSE ? HB : 1];
     bool requested = false;                          // r / vv hold the rows of the first HB hits of `cur`
-    if (b_lo < b_hi && PBSO_SCAN_STOP > 1) {
+    if (b_lo < b_hi) {
         decode(b_lo, cur);
-        if (cur.hit_mask && PBSO_SCAN_STOP > 2) {
+        if (cur.hit_mask) {
             int jj[HB];
             unsigned long long m = cur.hit_mask;
             const int nh = take_hits(m, jj);
@@ -289,14 +285,9 @@ __device__ __forceinline__ void scan_body(
             requested = true;
         }
     }
-    for (int base = b_lo; base < b_hi && PBSO_SCAN_STOP > 1; base += BATCH) {
+    for (int base = b_lo; base < b_hi; base += BATCH) {
         const int nd = b_hi - base < BATCH ? b_hi - base : BATCH;
         const bool more = base + BATCH < b_hi;
-        if (PBSO_SCAN_STOP <= 2) {
-            x.x += (float)(cur.hit_mask ^ cur.skip_mask ^ cur.dense_mask ^ cur.mark_mask) + cur.w[0] + (float)cur.prow + (float)cur.ptr;
-            if (more) decode(base + BATCH, cur);
-            continue;
-        }
         // ---- (2) the gains of the batch's hits, [buffer][mode] in LDS
         wave_sync();                                 // (the previous batch's reads are done)
         {
@@ -324,12 +315,6 @@ __device__ __forceinline__ void scan_body(
                 requested = true;
             }
         }
-        if (PBSO_SCAN_STOP <= 3) {
-            x.x += lds_g[lane & (BATCH - 1)][lane];
-            if (more) cur = nxt;
-            continue;
-        }
-
         // ---- (3) the scan, lane = mode: the gains of a group of G buffers are read from LDS TWO groups ahead (two register sets)
         const unsigned long long slow_mask = cur.skip_mask, mark_mask = cur.mark_mask;
         if constexpr (SEG) n_stepped += nd - __builtin_popcountll(slow_mask);
@@ -456,13 +441,11 @@ __device__ __forceinline__ void scan_body(
 
 template <bool DIRECT, bool DENSE>
 __global__ __launch_bounds__(64) void iir_scan_kernel(PBSO_SCAN_ARGS) {
-    prep_prio();
     scan_body<DIRECT, DENSE, false>(p_sq, p_sd, p_ss, p_sc, p_desc, p_grows, p_g32, p_g32_off, p_vinc, p_xfer_init, p_xs, p_xtrow, p);
 }
 
 template <bool DIRECT, bool DENSE>
 __global__ __launch_bounds__(64 * SEG_MAX) void iir_scan_seg_kernel(PBSO_SCAN_ARGS) {
-    prep_prio();
     scan_body<DIRECT, DENSE, true>(p_sq, p_sd, p_ss, p_sc, p_desc, p_grows, p_g32, p_g32_off, p_vinc, p_xfer_init, p_xs, p_xtrow, p);
 }
 #undef PBSO_SCAN_ARGS
@@ -490,7 +473,6 @@ struct IncDims {
 __global__ __launch_bounds__(64 * INC_NW) void dense_increment_kernel(
     const float *__restrict__ p_pc, const float *__restrict__ p_ftab, const float *__restrict__ p_tprof,
     const int *__restrict__ p_row_obj, const int *__restrict__ p_n_modes, float *__restrict__ p_vinc, const IncDims p) {
-    prep_prio();
     __shared__ __attribute__((aligned(16))) float lds_u[INC_NW][64 * U_ROW];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
