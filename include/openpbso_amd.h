@@ -379,6 +379,27 @@ void *pbso_audio_device_ptr(pbso_engine *e);
  * tools/real_time_modal_sound.cpp:192-212); also the per-rank half of PBSO_GATHER_MIX below.  Asynchronous on the engine's stream. */
 int pbso_mix_objects(pbso_engine *e, void *d_out);
 
+/* Scene mix: the step's audio placed in C output channels (1 <= C <= 8) -- a stereo or multichannel stream -- on the device.
+ * Every (channel, object) pair has a gain and a fractional delay in samples (the FFAT transfer gives a magnitude but no time of
+ * flight; the caller owns the geometry and computes both):
+ *     out_c(t) = sum_o g_co(t) * x_o(t - d_co(t)),  summed in object order as the object mix above (groups of 32, then the groups)
+ * t counts mixed samples from the enable (or the last reset), 64-bit; x_o(i) is object o's audio at absolute sample i across
+ * steps, 0 for i < 0; a fractional read position i0 + f is x(i0) + f (x(i0 + 1) - x(i0)), a fraction of exactly 0 reads x(i0).
+ * A set call takes effect at t_set = the first sample of the next mixed step and ramps each parameter over R = ramp_samples:
+ * p(t) = p_from + (p_to - p_from) (t - t_set + 1) / R until t = t_set + R - 1, p_to from then on (at once for R = 0); a set
+ * during a ramp starts from the current value p(t_set - 1); the first set after enable / reset takes effect without a ramp;
+ * until then every gain and delay is 0 (silence).  The output depends on the rows, the values set and the absolute samples at
+ * which they took effect only -- not on how the samples are cut into steps.  The last max_delay + 1 samples of every object
+ * are kept on the device, so delays reach back across steps; hence, while the mixer is enabled, every step (pbso_step /
+ * pbso_step_into) is mixed exactly once: a mix after a step that was not mixed, a second mix of the same step, or a mix after a
+ * step delivered to host memory (the rows are not on the device) is PBSO_ERR_STATE.  The reset clears the history to silence,
+ * restarts t at 0, keeps the gains and delays last set (ramps finished) and arms the mixer for the next step.              */
+int pbso_scene_mix_enable(pbso_engine *e, int n_channels, int max_delay, int ramp_samples);  /* after finalize; max_delay, ramp <= 1 << 20 */
+int pbso_scene_mix_set(pbso_engine *e, const float *gain, const float *delay);  /* [C][n_objects] each; delay NULL = unchanged */
+int pbso_scene_mix(pbso_engine *e, void *d_out);           /* the last step, async on the engine's stream: d_out [C][n_buffers * B] f32, or NULL = engine-owned */
+int pbso_read_scene_mix(pbso_engine *e, float *host_out, size_t n);   /* the last mix, synchronously; n = C * n_buffers * B */
+int pbso_scene_mix_reset(pbso_engine *e);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a
@@ -391,8 +412,12 @@ enum pbso_gather_mode {
     PBSO_GATHER_ALL = 1,      /* every rank receives every object's buffers: ncclAllGather, in place (each engine writes its buffers
                                  straight into its slice of the gather target) */
     PBSO_GATHER_ROOT = 2,     /* only rank 0 receives them: ncclSend / ncclRecv */
-    PBSO_GATHER_MIX = 3       /* the consumer wants ONE mixed stream: every rank sums its objects' buffers on the device
+    PBSO_GATHER_MIX = 3,      /* the consumer wants ONE mixed stream: every rank sums its objects' buffers on the device
                                  (pbso_mix_objects) and the ranks all-reduce n_buffers * 513 floats */
+    PBSO_GATHER_SCENE = 4     /* the scene mix: every rank mixes its own objects into C channels (the scene mix above; an empty rank
+                                 contributes silence) and the ranks all-reduce C * n_buffers * 513 floats.  While the group's mixer is
+                                 enabled, every group step is gathered this way exactly once (a second time: PBSO_ERR_STATE); the
+                                 other modes can still be gathered for that step */
 };
 #define PBSO_GROUP_ID_BYTES 128
 enum pbso_group_transport {
@@ -440,9 +465,14 @@ int pbso_group_step(pbso_group *g, int n_buffers);
 /* the collective for the LAST step, asynchronous (its own stream per rank, ordered behind the step); enum pbso_gather_mode  */
 int pbso_group_gather(pbso_group *g, int mode);
 int pbso_group_sync(pbso_group *g);
+/* the scene mixer on every local rank; gain / delay [C][n_objects of the whole job] by global id (each rank takes the slice of
+ * its own objects).  After pbso_group_finalize; the arguments as for a single engine.                                       */
+int pbso_group_scene_mix_enable(pbso_group *g, int n_channels, int max_delay, int ramp_samples);
+int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *delay);
 /* the last gather's result on a local rank, a device pointer: ALL -> [world_size * rows_per_rank][n_buffers * 513] (rank r's
  * objects from row r * rows_per_rank; shards smaller than the largest are padded with silent rows), ROOT -> the same on rank 0
- * and the rank's own rows elsewhere, MIX -> [n_buffers * 513].  rows / row_floats (may be NULL) receive the shape.          */
+ * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE -> [C][n_buffers * 513].  rows / row_floats (may be NULL)
+ * receive the shape.                                                                                                        */
 void *pbso_group_result_device_ptr(pbso_group *g, int rank, size_t *rows, size_t *row_floats);
 int pbso_group_read_result(pbso_group *g, int rank, float *host_out, size_t n_floats);   /* that buffer, synchronously */
 

@@ -28,13 +28,15 @@ EXPORTS = [
     "pbso_modes_read", "pbso_num_modes_audible", "pbso_material_read", "pbso_free", "pbso_read_census", "pbso_obj_read", "pbso_arprm_pending", "pbso_flush",
     "pbso_mix_objects", "pbso_read_audio_rows", "pbso_compute_transfer_path",
     "pbso_step_to_host", "pbso_host_wait", "pbso_host_alloc", "pbso_host_free",
+    # the scene mix (C channels, a ramped gain and fractional delay per channel and object)
+    "pbso_scene_mix_enable", "pbso_scene_mix_set", "pbso_scene_mix", "pbso_read_scene_mix", "pbso_scene_mix_reset",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
     "pbso_group_enqueue_force", "pbso_group_step", "pbso_group_gather", "pbso_group_sync", "pbso_group_result_device_ptr",
-    "pbso_group_read_result", "pbso_shard_by_modes",
+    "pbso_group_read_result", "pbso_shard_by_modes", "pbso_group_scene_mix_enable", "pbso_group_scene_mix_set",
 ]
-GATHER_ALL, GATHER_ROOT, GATHER_MIX = 1, 2, 3
+GATHER_ALL, GATHER_ROOT, GATHER_MIX, GATHER_SCENE = 1, 2, 3, 4
 GROUP_ID_BYTES = 128
 
 
@@ -164,6 +166,14 @@ def lib():
     l.pbso_free.argtypes = [vp]
     l.pbso_free.restype = None
     l.pbso_mix_objects.argtypes = [vp, vp]
+    fp = C.POINTER(C.c_float)
+    l.pbso_scene_mix_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    l.pbso_scene_mix_set.argtypes = [vp, fp, fp]
+    l.pbso_scene_mix.argtypes = [vp, vp]
+    l.pbso_read_scene_mix.argtypes = [vp, fp, C.c_size_t]
+    l.pbso_scene_mix_reset.argtypes = [vp]
+    l.pbso_group_scene_mix_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    l.pbso_group_scene_mix_set.argtypes = [vp, fp, fp]
     l.pbso_step_to_host.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     l.pbso_host_wait.argtypes = [vp]
     l.pbso_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

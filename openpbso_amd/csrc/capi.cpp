@@ -405,6 +405,45 @@ int pbso_mix_objects(pbso_engine *e, void *d_out) {
     GUARD_END(e)
 }
 
+int pbso_scene_mix_enable(pbso_engine *e, int n_channels, int max_delay, int ramp_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_mix_enable(n_channels, max_delay, ramp_samples);
+    GUARD_END(e)
+}
+
+int pbso_scene_mix_set(pbso_engine *e, const float *gain, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_mix_set(gain, delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_mix(pbso_engine *e, void *d_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_mix(d_out);
+    GUARD_END(e)
+}
+
+int pbso_read_scene_mix(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_scene_mix(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_scene_mix_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_mix_reset();
+    GUARD_END(e)
+}
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

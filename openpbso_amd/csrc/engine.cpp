@@ -209,6 +209,7 @@ Engine::~Engine() {
     delete pool_;
     delete submit_;                                    // (the worker makes what it still holds, then ends)
     submit_ = nullptr;
+    scene_mix_release();
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (aux_stream_) (void)hipStreamSynchronize(aux_stream_);
     if (timeline_have_base_) {                         // (the reference launch's quad was kept out of the free list)
@@ -3040,6 +3041,7 @@ int Engine::step_to_host(int nb, float *host_out, size_t n) {
         if (hipPointerGetAttributes(&attr, host_out) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) {
             int rc = step(nb, attr.devicePointer);
             if (rc != PBSO_OK) return rc;
+            host_step_ = tot_steps_;
             if ((rc = drain_submit()) != PBSO_OK) return rc;          // (the event below goes behind the step's launches)
             HIPTRY(hipEventRecord(ev_host_copy_[slot], stream_));      // "delivered" = the bank (and what follows it) has finished
             host_last_ = slot;
@@ -3052,6 +3054,7 @@ int Engine::step_to_host(int nb, float *host_out, size_t n) {
     HIPTRY(hipStreamWaitEvent(stream_, ev_host_copy_[slot], 0));          // the copy that last read this buffer is done
     int rc = step(nb, d_audio_host_[slot].p);
     if (rc != PBSO_OK) return rc;
+    host_step_ = tot_steps_;
     if ((rc = drain_submit()) != PBSO_OK) return rc;
     HIPTRY(hipEventRecord(ev_host_bank_[slot], stream_));
     HIPTRY(hipStreamWaitEvent(copy_stream_, ev_host_bank_[slot], 0));

@@ -22,6 +22,7 @@
 
 namespace pbso {
 class SubmitQueue;       // submit_queue.h
+struct SceneMix;         // scene_mix.cpp
 
 // ---- growable device / pinned-host buffers ---------------------------------
 template <class T>
@@ -196,6 +197,12 @@ public:
     int listeners_enable(int obj);
     int mix_listeners(int obj, const double *pos, int n_listeners, float *out, size_t n_out);
     int mix_objects(void *d_out);
+    // the scene mixer (scene_mix.cpp, kernels_mix.hip): C channels, a ramped gain and a fractional delay per (channel, object)
+    int scene_mix_enable(int n_channels, int max_delay, int ramp_samples);
+    int scene_mix_set(const float *gain, const float *delay);
+    int scene_mix(void *d_out);
+    int read_scene_mix(float *out, size_t n);
+    int scene_mix_reset();
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -396,6 +403,9 @@ private:
     unsigned launch_seq_ = 0;                            // PBSO_ROTATE_PRIO: see kernels_iir.hip
     float *last_audio_ = nullptr;
     int last_nb_ = 0;
+    int64_t host_step_ = -1;                             // tot_steps_ of the last pbso_step_to_host (its rows may be in host memory)
+    SceneMix *scene_ = nullptr;                          // pbso_scene_mix_enable
+    void scene_mix_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -80,6 +81,9 @@ struct Rank {
     float *mix[2] = {nullptr, nullptr};                  // [row]
     float *scratch = nullptr;                            // RCCL_ALWAYS, one rank: where the send to itself lands; LOOPBACK: [world][row] mix rows + the sum's partial rows
     size_t target_floats = 0, mix_floats = 0, scratch_floats = 0;
+    float *scene[2] = {nullptr, nullptr};                // PBSO_GATHER_SCENE: [C][row]
+    float *scene_scratch = nullptr;                      // ... LOOPBACK: [world][C * row] the ranks' mixes + the sum's partial rows + the result
+    size_t scene_floats = 0, scene_scratch_floats = 0;
     hipEvent_t ev_step[2] = {nullptr, nullptr}, ev_coll[2] = {nullptr, nullptr};
     int n_local = 0, next_local = 0;
 };
@@ -96,6 +100,8 @@ struct pbso_group {
     int slot = 0, last_nb = 0, last_mode = 0, last_slot = -1;
     bool stepped = false;
     int transport = PBSO_GROUP_RCCL;
+    int scene_c = 0, scene_max_delay = 0;                // the scene mixer (pbso_group_scene_mix_enable)
+    bool scene_on = false, scene_mixed = false;          // ... and whether the last step has had its PBSO_GATHER_SCENE
     bool use_rccl = false;                               // a communicator exists: the collectives go through librccl
     bool loopback() const { return transport == PBSO_GROUP_LOOPBACK; }
     std::string err;
@@ -147,6 +153,11 @@ float *loop_mix_out(const pbso_group *g, const Rank &rk, size_t row) {
     return rk.scratch + (size_t)(g->world + pbso::mix_objects_groups(g->world)) * row;
 }
 
+// loopback all-reduce of the scene mix: [world scene mixes | partial rows of the sum | the result], each C * row floats
+float *scene_loop_out(const pbso_group *g, const Rank &rk, size_t count) {
+    return rk.scene_scratch + (size_t)(g->world + pbso::mix_objects_groups(g->world)) * count;
+}
+
 Rank *local_rank(pbso_group *g, int rank) {
     const int i = rank - g->first;
     return i >= 0 && i < (int)g->ranks.size() ? &g->ranks[i] : nullptr;
@@ -183,6 +194,38 @@ int ensure_buffers(pbso_group *g, Rank &rk, int nb, int mode) {
         if (rk.scratch) GHIP(g, hipFree(rk.scratch));
         GHIP(g, hipMalloc(&rk.scratch, want_scratch * sizeof(float)));
         rk.scratch_floats = want_scratch;
+    }
+    return PBSO_OK;
+}
+
+// the scene mix's buffers of every local rank: count = C * row floats (a block that grows is freed once nothing reads it: the
+// loopback ranks' collectives read each other's)
+int ensure_scene_buffers(pbso_group *g, size_t count) {
+    const size_t want_scratch = g->loopback() ? count * (size_t)(g->world + pbso::mix_objects_groups(g->world) + 1) : 0;
+    bool grow = false;
+    for (Rank &rk : g->ranks) grow = grow || count > rk.scene_floats || want_scratch > rk.scene_scratch_floats;
+    if (!grow) return PBSO_OK;
+    for (Rank &rk : g->ranks) {
+        GHIP(g, hipSetDevice(rk.device));
+        GHIP(g, hipStreamSynchronize(rk.stream));
+        GHIP(g, hipStreamSynchronize(rk.coll));
+    }
+    for (Rank &rk : g->ranks) {
+        GHIP(g, hipSetDevice(rk.device));
+        if (count > rk.scene_floats) {
+            for (float *&p : rk.scene) {
+                if (p) GHIP(g, hipFree(p));
+                p = nullptr;
+                GHIP(g, hipMalloc(&p, count * sizeof(float)));
+            }
+            rk.scene_floats = count;
+        }
+        if (want_scratch > rk.scene_scratch_floats) {
+            if (rk.scene_scratch) GHIP(g, hipFree(rk.scene_scratch));
+            rk.scene_scratch = nullptr;
+            GHIP(g, hipMalloc(&rk.scene_scratch, want_scratch * sizeof(float)));
+            rk.scene_scratch_floats = want_scratch;
+        }
     }
     return PBSO_OK;
 }
@@ -296,6 +339,8 @@ void pbso_group_destroy(pbso_group *g) {
         for (int s = 0; s < 2; ++s) {
             if (rk.target[s]) (void)hipFree(rk.target[s]);
             if (rk.mix[s]) (void)hipFree(rk.mix[s]);
+            if (rk.scene[s]) (void)hipFree(rk.scene[s]);
+            if (s == 0 && rk.scene_scratch) (void)hipFree(rk.scene_scratch);
             if (s == 0 && rk.scratch) (void)hipFree(rk.scratch);
             if (rk.ev_step[s]) (void)hipEventDestroy(rk.ev_step[s]);
             if (rk.ev_coll[s]) (void)hipEventDestroy(rk.ev_coll[s]);
@@ -431,6 +476,51 @@ int pbso_group_step(pbso_group *g, int nb) {
     g->last_mode = 0;
     g->slot ^= 1;
     g->stepped = true;
+    g->scene_mixed = false;
+    return PBSO_OK;
+}
+
+int pbso_group_scene_mix_enable(pbso_group *g, int n_channels, int max_delay, int ramp_samples) {
+    if (!g || !g->finalized) return gfail(g, PBSO_ERR_STATE, "scene_mix_enable before finalize");
+    if (n_channels < 1 || n_channels > pbso::SCENE_MAX_CHANNELS || max_delay < 0 || max_delay > (1 << 20) || ramp_samples < 0 ||
+        ramp_samples > (1 << 20))
+        return gfail(g, PBSO_ERR_INVALID, "scene_mix_enable: n_channels 1 .. 8, max_delay and ramp_samples 0 .. 1 << 20");
+    for (Rank &rk : g->ranks)                            // (an empty rank has no engine to mix: it contributes silence)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_mix_enable(rk.eng, n_channels, max_delay, ramp_samples));
+    g->scene_on = true;
+    g->scene_c = n_channels;
+    g->scene_max_delay = max_delay;
+    g->scene_mixed = true;                               // (armed for the next step, as every engine is)
+    return PBSO_OK;
+}
+
+int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *delay) {
+    if (!g || !g->scene_on) return gfail(g, PBSO_ERR_STATE, "scene_mix_set: the group's scene mixer is not enabled");
+    if (!gain) return gfail(g, PBSO_ERR_INVALID, "scene_mix_set: gain is NULL");
+    const size_t n = (size_t)g->n_objects, cn = (size_t)g->scene_c * n;
+    // checked for the whole job first: no rank takes a set that another one refuses
+    for (size_t i = 0; i < cn; ++i) {
+        if (!std::isfinite(gain[i])) return gfail(g, PBSO_ERR_INVALID, "scene_mix_set: a gain is not finite");
+        if (delay && !(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)g->scene_max_delay))
+            return gfail(g, PBSO_ERR_INVALID, "scene_mix_set: a delay is not finite or outside [0, max_delay]");
+    }
+    try {
+        std::vector<float> gs, ds;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local;
+            gs.resize((size_t)g->scene_c * nl);
+            ds.resize(delay ? gs.size() : 0);
+            for (int c = 0; c < g->scene_c; ++c)
+                for (size_t l = 0; l < nl; ++l) {
+                    gs[c * nl + l] = gain[c * n + lo + l];
+                    if (delay) ds[c * nl + l] = delay[c * n + lo + l];
+                }
+            GENG(g, rk, pbso_scene_mix_set(rk.eng, gs.data(), delay ? ds.data() : nullptr));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
     return PBSO_OK;
 }
 
@@ -440,9 +530,27 @@ static constexpr size_t P2P_MAX = (size_t)64 << 20;      // floats
 
 int pbso_group_gather(pbso_group *g, int mode) {
     if (!g || !g->stepped) return gfail(g, PBSO_ERR_STATE, "gather before step");
-    if (mode != PBSO_GATHER_ALL && mode != PBSO_GATHER_ROOT && mode != PBSO_GATHER_MIX) return gfail(g, PBSO_ERR_INVALID, "gather mode");
+    if (mode != PBSO_GATHER_ALL && mode != PBSO_GATHER_ROOT && mode != PBSO_GATHER_MIX && mode != PBSO_GATHER_SCENE)
+        return gfail(g, PBSO_ERR_INVALID, "gather mode");
     const int slot = g->last_slot;
     const size_t row = (size_t)g->last_nb * g->frames, blk = (size_t)g->cmax * row;
+    const size_t scount = (size_t)g->scene_c * row;      // PBSO_GATHER_SCENE: floats of one rank's mix
+    if (mode == PBSO_GATHER_SCENE) {
+        if (!g->scene_on) return gfail(g, PBSO_ERR_STATE, "scene gather: the group's scene mixer is not enabled");
+        if (g->scene_mixed) return gfail(g, PBSO_ERR_STATE, "scene gather: this step is mixed already (or was taken before the mixer was enabled)");
+        int rc = ensure_scene_buffers(g, scount);
+        if (rc != PBSO_OK) return rc;
+        for (Rank &rk : g->ranks) {
+            GHIP(g, hipSetDevice(rk.device));
+            // (the collective that last read this slot's mix is done)
+            if (g->loopback()) for (Rank &other : g->ranks) GHIP(g, hipStreamWaitEvent(rk.stream, other.ev_coll[slot], 0));
+            else GHIP(g, hipStreamWaitEvent(rk.stream, rk.ev_coll[slot], 0));
+            if (rk.n_local > 0) GENG(g, rk, pbso_scene_mix(rk.eng, rk.scene[slot]));
+            else GHIP(g, hipMemsetAsync(rk.scene[slot], 0, scount * sizeof(float), rk.stream));
+            GHIP(g, hipEventRecord(rk.ev_step[slot], rk.stream));
+        }
+        g->scene_mixed = true;
+    }
     if (mode == PBSO_GATHER_MIX) {
         for (Rank &rk : g->ranks) {
             GHIP(g, hipSetDevice(rk.device));
@@ -468,6 +576,8 @@ int pbso_group_gather(pbso_group *g, int mode) {
                 GNCCL_OPEN(g, g_rccl.AllGather(mine, base, blk, ncclFloat, rk.comm, rk.coll));          // in place: sendbuff == recvbuff + rank * count
             } else if (mode == PBSO_GATHER_MIX) {
                 GNCCL_OPEN(g, g_rccl.AllReduce(rk.mix[slot], rk.mix[slot], row, ncclFloat, ncclSum, rk.comm, rk.coll));
+            } else if (mode == PBSO_GATHER_SCENE) {
+                GNCCL_OPEN(g, g_rccl.AllReduce(rk.scene[slot], rk.scene[slot], scount, ncclFloat, ncclSum, rk.comm, rk.coll));
             } else if (g->world == 1) {
                 // (PBSO_GROUP_RCCL_ALWAYS: the root's receive and a rank's send, both on the one rank there is -- the rows land in
                 //  the scratch rows, which is what pbso_group_result_device_ptr then hands out)
@@ -503,6 +613,13 @@ int pbso_group_gather(pbso_group *g, int mode) {
                 // (into a row of its own: the other ranks' copies still read this rank's mix row)
                 int lrc = pbso::launch_mix_objects(rows, g->world, (long long)row, (long long)row, parts, loop_mix_out(g, rk, row), rk.coll);
                 if (lrc != 0) return gfail(g, PBSO_ERR_HIP, "loopback all-reduce: launch_mix_objects");
+            } else if (mode == PBSO_GATHER_SCENE) {
+                // the same for the ranks' C channels, as one row of C * row floats per rank: summed in rank order
+                float *rows = rk.scene_scratch, *parts = rk.scene_scratch + (size_t)g->world * scount;
+                for (Rank &src : g->ranks)
+                    GHIP(g, hipMemcpyAsync(rows + (size_t)src.rank * scount, src.scene[slot], scount * sizeof(float), hipMemcpyDeviceToDevice, rk.coll));
+                int lrc = pbso::launch_mix_objects(rows, g->world, (long long)scount, (long long)scount, parts, scene_loop_out(g, rk, scount), rk.coll);
+                if (lrc != 0) return gfail(g, PBSO_ERR_HIP, "loopback all-reduce: launch_mix_objects");
             }
         }
     }
@@ -533,6 +650,10 @@ void *pbso_group_result_device_ptr(pbso_group *g, int rank, size_t *rows, size_t
     if (g->last_mode == PBSO_GATHER_MIX) {
         if (rows) *rows = 1;
         return g->loopback() ? loop_mix_out(g, *rk, row) : rk->mix[g->last_slot];
+    }
+    if (g->last_mode == PBSO_GATHER_SCENE) {
+        if (rows) *rows = (size_t)g->scene_c;
+        return g->loopback() ? scene_loop_out(g, *rk, (size_t)g->scene_c * row) : rk->scene[g->last_slot];
     }
     const bool full = g->last_mode == PBSO_GATHER_ALL || (g->last_mode == PBSO_GATHER_ROOT && rk->rank == 0);
     if (rows) *rows = full ? (size_t)g->world * g->cmax : (size_t)g->cmax;

@@ -299,6 +299,17 @@ int launch_copy_rows(const int *src_row, const int *dst_row, int n, double *rows
 int mix_objects_groups(int n_obj);
 int launch_mix_objects(const float *audio, int n_obj, long long stride, long long n, float *parts, float *out, hipStream_t stream);
 
+// pbso_scene_mix (kernels_mix.hip): C output channels, a ramped gain and fractional delay per (channel, object).  One parameter's
+// ramp: p(t) = to once t >= t_set + R - 1 (or R == 0), else from + slope (t - t_set + 1) with slope = (to - from) / R stored
+// by the host, in fp64 (t: absolute sample)
+struct SceneParam { double from, to; long long t_set; double slope; };
+constexpr int SCENE_MAX_CHANNELS = 8;
+// out[c][i] = sum_o g_co(t) x_o(t - d_co(t)), t = t0 + i, i < n; params [C][n_obj][2] (gain, delay); rows [n_obj][n] (the step);
+// hist [n_obj][H] the H samples before it.  parts: C x mix_objects_groups(n_obj) x n floats.  Then hist_next = the last H
+// samples of hist ++ rows (a second kernel on the stream: the mix has read hist by then)
+int launch_scene_mix(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const SceneParam *params,
+                     int C, int ramp, long long t0, float *parts, float *out, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -134,6 +134,19 @@ class Group:
     def gather(self, mode=capi.GATHER_ALL):
         self._chk(self._l.pbso_group_gather(self._h, mode))
 
+    def scene_mix_enable(self, n_channels, max_delay, ramp_samples=0):
+        """pbso_group_scene_mix_enable: every group step is then gathered once with GATHER_SCENE"""
+        self._chk(self._l.pbso_group_scene_mix_enable(self._h, n_channels, max_delay, ramp_samples))
+        self._scene_c = n_channels
+
+    def scene_mix_set(self, gain, delay=None):
+        """pbso_group_scene_mix_set: gain / delay [n_channels][n_objects of the job] by global id; delay None keeps the delays"""
+        fp = C.POINTER(C.c_float)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        assert g.size == self._scene_c * len(self._modes) and (d is None or d.size == g.size)
+        self._chk(self._l.pbso_group_scene_mix_set(self._h, g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
+
     def sync(self):
         self._chk(self._l.pbso_group_sync(self._h))
 

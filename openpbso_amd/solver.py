@@ -505,6 +505,34 @@ class Engine:
         """pbso_mix_objects: the last step's audio summed over the objects, into the device buffer d_out [n_buffers * 513] f32"""
         self._chk(self._l.pbso_mix_objects(self._h, C.c_void_p(d_out)))
 
+    # -- scene mix: C channels, a ramped gain and a fractional delay (samples) per (channel, object) -------------------------
+    def scene_mix_enable(self, n_channels, max_delay, ramp_samples=0):
+        """pbso_scene_mix_enable: from the next step on, every step is mixed exactly once (scene_mix)"""
+        self._chk(self._l.pbso_scene_mix_enable(self._h, n_channels, max_delay, ramp_samples))
+        self._scene_c, self._scene_nb = n_channels, 0
+
+    def scene_mix_set(self, gain, delay=None):
+        """pbso_scene_mix_set: gain / delay [n_channels][n_objects]; delay None keeps the delays"""
+        fp = C.POINTER(C.c_float)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        assert g.size == self._scene_c * len(self.n_modes) and (d is None or d.size == g.size)
+        self._chk(self._l.pbso_scene_mix_set(self._h, g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
+
+    def scene_mix(self, d_out=None):
+        """pbso_scene_mix: the last step into the device buffer d_out [n_channels][n_buffers * 513] f32 (None: the engine's own)"""
+        self._chk(self._l.pbso_scene_mix(self._h, None if d_out is None else C.c_void_p(d_out)))
+        self._scene_nb = self._last_nb
+
+    def read_scene_mix(self):
+        """the last scene mix: [n_channels][n_buffers * 513] float32 (synchronous)"""
+        out = np.empty((self._scene_c, self._scene_nb * self.B), dtype=np.float32)
+        self._chk(self._l.pbso_read_scene_mix(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def scene_mix_reset(self):
+        self._chk(self._l.pbso_scene_mix_reset(self._h))
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

@@ -17,8 +17,13 @@
 //                    modes, RCCL only for the final collective): the scene is --copies K instances of the object (default: one
 //                    per device), copy c hears the hit and listener scripts c * --copy-shift buffers later (default 1), and
 //                    the WAV is their MIX (PBSO_GATHER_MIX: every GPU sums its objects, the GPUs all-reduce one row)
+//   --channels C --pan FILE [--ramp N]   a C-channel scene mix (pbso_scene_mix; with --devices PBSO_GATHER_SCENE) instead of the
+//                    mono one: lines <buffer> <copy> <g_0> <d_0> ... <g_{C-1}> <d_{C-1}> set copy's gain and delay (samples) per
+//                    channel from that buffer on, ramped over N samples (default 441); the tool steps the segments between
+//                    these change points, mixes each, and writes a C-channel interleaved float32 WAV (--raw: the same frames)
 #include <dirent.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -53,11 +58,11 @@ static std::string guess_name(const std::string &dir) {
     return found.substr(0, found.find_first_of("."));
 }
 
-static void write_wav_f32(const std::string &path, const std::vector<float> &mono, int rate) {
+static void write_wav_f32(const std::string &path, const std::vector<float> &mono, int rate, int channels = 1) {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) die("cannot write " + path);
-    const uint32_t data_bytes = (uint32_t)(mono.size() * 4), riff = 36 + data_bytes, fmt_len = 16, byte_rate = rate * 4;
-    const uint16_t fmt = 3 /* IEEE float */, ch = 1, align = 4, bits = 32;
+    const uint32_t data_bytes = (uint32_t)(mono.size() * 4), riff = 36 + data_bytes, fmt_len = 16, byte_rate = rate * 4 * channels;
+    const uint16_t fmt = 3 /* IEEE float */, ch = (uint16_t)channels, align = (uint16_t)(4 * channels), bits = 32;
     const uint32_t r = rate;
     std::fwrite("RIFF", 1, 4, f); std::fwrite(&riff, 4, 1, f); std::fwrite("WAVEfmt ", 1, 8, f);
     std::fwrite(&fmt_len, 4, 1, f); std::fwrite(&fmt, 2, 1, f); std::fwrite(&ch, 2, 1, f);
@@ -69,11 +74,38 @@ static void write_wav_f32(const std::string &path, const std::vector<float> &mon
 
 struct Hit { long b; pbso_force_msg m; };
 struct Pos { long b; double p[3]; };
+// --channels / --pan: the scene mix's script
+struct Pan { long b; int copy; std::vector<float> gd; };   // gd: g_0 d_0 ... g_{C-1} d_{C-1}
+struct Scene {
+    int channels = 0, ramp = 441, copies = 1, max_delay = 0;
+    std::vector<Pan> lines;
+    // segments [cuts[k], cuts[k + 1]) between the change points; set_at(b) updates gain / delay [C][copies] for buffer b
+    std::vector<int> cuts(int n_buffers) const {
+        std::vector<int> c{0, n_buffers};
+        for (const Pan &p : lines)
+            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+        std::sort(c.begin(), c.end());
+        c.erase(std::unique(c.begin(), c.end()), c.end());
+        return c;
+    }
+    bool set_at(long b, std::vector<float> &gain, std::vector<float> &delay) const {
+        bool any = false;
+        for (const Pan &p : lines)
+            if (p.b == b) {
+                for (int c = 0; c < channels; ++c) {
+                    gain[(size_t)c * copies + p.copy] = p.gd[2 * c];
+                    delay[(size_t)c * copies + p.copy] = p.gd[2 * c + 1];
+                }
+                any = true;
+            }
+        return any;
+    }
+};
 
 // the scene on several GPUs (include/openpbso_amd.h "device group")
 static int run_group(const std::vector<int> &devices, int copies, int shift, const std::string &modes, const std::string &material,
                      const std::string &ffat, const std::vector<Hit> &hits, const std::vector<Pos> &path, int n_buffers,
-                     std::vector<float> &sound) {
+                     const Scene *scene, std::vector<float> &sound) {
     auto gcheck = [](pbso_group *g, int rc, const char *what) {
         if (rc < 0) die(std::string(what) + ": " + pbso_status_string(rc) + ": " + (g ? pbso_group_last_error(g) : ""));
     };
@@ -127,10 +159,32 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             if (rc == 0) die("force queue full");
         }
     }
-    gcheck(g, pbso_group_step(g, n_buffers), "group_step");
-    gcheck(g, pbso_group_gather(g, PBSO_GATHER_MIX), "group_gather");
-    sound.resize((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
-    gcheck(g, pbso_group_read_result(g, 0, sound.data(), sound.size()), "group_read_result");
+    if (scene) {
+        // the segments between the pan script's change points, each gathered as a C-channel scene mix: sound [C][n_buffers * B]
+        const int C = scene->channels;
+        const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
+        gcheck(g, pbso_group_scene_mix_enable(g, C, scene->max_delay, scene->ramp), "group_scene_mix_enable");
+        std::vector<float> gain((size_t)C * copies, 0.f), delay((size_t)C * copies, 0.f), seg;
+        sound.assign((size_t)C * total, 0.f);
+        const std::vector<int> cuts = scene->cuts(n_buffers);
+        for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+            if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
+            const int nb = cuts[k + 1] - cuts[k];
+            const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
+            gcheck(g, pbso_group_step(g, nb), "group_step");
+            gcheck(g, pbso_group_gather(g, PBSO_GATHER_SCENE), "group_gather");
+            seg.resize((size_t)C * row);
+            gcheck(g, pbso_group_read_result(g, 0, seg.data(), seg.size()), "group_read_result");
+            for (int c = 0; c < C; ++c)
+                std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
+                          sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
+        }
+    } else {
+        gcheck(g, pbso_group_step(g, n_buffers), "group_step");
+        gcheck(g, pbso_group_gather(g, PBSO_GATHER_MIX), "group_gather");
+        sound.resize((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
+        gcheck(g, pbso_group_read_result(g, 0, sound.data(), sound.size()), "group_read_result");
+    }
     std::printf("%d copies x %d audible modes on %d device(s): ranks own", copies, n_aud, (int)devices.size());
     for (int r = 0; r < (int)devices.size(); ++r) {
         int lo = 0, hi = 0;
@@ -143,8 +197,9 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, listener, out = "out.wav", raw, devices_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, listener, out = "out.wav", raw, devices_arg, pan;
     int n_buffers = 86, copies = 0, copy_shift = 1;
+    Scene scene;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + a); return argv[++i]; };
@@ -162,6 +217,9 @@ int main(int argc, char **argv) {
         else if (a == "--devices") devices_arg = val();
         else if (a == "--copies") copies = std::atoi(val().c_str());
         else if (a == "--copy-shift") copy_shift = std::atoi(val().c_str());
+        else if (a == "--channels") scene.channels = std::atoi(val().c_str());
+        else if (a == "--pan") pan = val();
+        else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else die("unknown flag " + a);
     }
     if (!d.empty()) {                                   // fixed directory structure, tools/...:480-495
@@ -248,15 +306,46 @@ int main(int argc, char **argv) {
         }
     }
 
-    std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
-    double device_ms = 0;
+    std::vector<int> devices;
     if (!devices_arg.empty()) {
-        std::vector<int> devices;
         std::istringstream ds(devices_arg);
         std::string tok;
         while (std::getline(ds, tok, ',')) devices.push_back(std::atoi(tok.c_str()));
         if (devices.empty()) die("--devices needs a list of HIP ordinals");
-        run_group(devices, copies > 0 ? copies : (int)devices.size(), copy_shift, modes, material, ffat, hit_list, path, n_buffers, sound);
+        if (copies <= 0) copies = (int)devices.size();
+    }
+    const bool mixed = scene.channels != 0 || !pan.empty();
+    if (mixed) {
+        // the scene mix's script: <buffer> <copy> then a gain and a delay per channel
+        if (scene.channels < 1 || scene.channels > 8) die("--channels must be 1 .. 8");
+        if (pan.empty()) die("--channels needs --pan FILE");
+        if (scene.ramp < 0 || scene.ramp > (1 << 20)) die("--ramp must be 0 .. 1048576");
+        scene.copies = devices.empty() ? 1 : copies;
+        std::ifstream f(pan);
+        if (!f) die("cannot read " + pan);
+        std::string line;
+        double dmax = 0;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            Pan p;
+            if (!(iss >> p.b >> p.copy)) die("bad pan line: " + line);
+            p.gd.resize(2 * (size_t)scene.channels);
+            for (float &v : p.gd)
+                if (!(iss >> v)) die("bad pan line (a gain and a delay per channel): " + line);
+            if (p.copy < 0 || p.copy >= scene.copies) die("pan line for a copy that does not exist: " + line);
+            if (p.b < 0 || p.b >= n_buffers) die("pan line outside buffers 0 .. --buffers - 1: " + line);
+            for (int c = 0; c < scene.channels; ++c)
+                if (!(p.gd[2 * c + 1] >= 0.f && p.gd[2 * c + 1] <= (float)(1 << 20))) die("pan delay outside [0, 1048576]: " + line);
+            for (int c = 0; c < scene.channels; ++c) dmax = std::max(dmax, (double)p.gd[2 * c + 1]);
+            scene.lines.push_back(p);
+        }
+        scene.max_delay = (int)std::ceil(dmax);
+    }
+    std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
+    double device_ms = 0;
+    if (!devices.empty()) {
+        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, path, n_buffers, mixed ? &scene : nullptr, sound);
     } else {
         pbso_engine_desc desc;
         std::memset(&desc, 0, sizeof(desc));
@@ -277,20 +366,47 @@ int main(int argc, char **argv) {
             check(e, rc, "enqueue_force");
             if (rc == 0) die("force queue full");
         }
-        check(e, pbso_step(e, n_buffers), "step");
-        check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
+        if (mixed) {
+            // the one object through the scene mixer, segment by segment: sound [C][n_buffers * B]
+            const int C = scene.channels;
+            const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
+            check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
+            std::vector<float> gain(C, 0.f), delay(C, 0.f), seg;
+            sound.assign((size_t)C * total, 0.f);
+            const std::vector<int> cuts = scene.cuts(n_buffers);
+            for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+                if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
+                const int nb = cuts[k + 1] - cuts[k];
+                const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
+                check(e, pbso_step(e, nb), "step");
+                check(e, pbso_scene_mix(e, nullptr), "scene_mix");
+                seg.resize((size_t)C * row);
+                check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
+                for (int c = 0; c < C; ++c)
+                    std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
+                              sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
+            }
+        } else {
+            check(e, pbso_step(e, n_buffers), "step");
+            check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
+        }
         pbso_engine_info info;
         check(e, pbso_get_info(e, &info), "get_info");
-        device_ms = info.last_step_device_ms;
+        device_ms = mixed ? info.total_device_ms : info.last_step_device_ms;      // (the scene mix steps in segments)
         pbso_engine_destroy(e);
     }
-    std::vector<float> mono(sound.size());
-    for (size_t i = 0; i < sound.size(); ++i) mono[i] = (float)((double)sound[i] / 1E10);   // tools/...:208
-    write_wav_f32(out, mono, PBSO_SAMPLE_RATE);
+    // C channels interleaved (mono: as it stands)
+    const int channels = mixed ? scene.channels : 1;
+    const size_t frames = sound.size() / channels;
+    std::vector<float> frames_raw(sound.size()), wav(sound.size());
+    for (size_t i = 0; i < frames; ++i)
+        for (int c = 0; c < channels; ++c) frames_raw[i * channels + c] = sound[(size_t)c * frames + i];
+    for (size_t i = 0; i < wav.size(); ++i) wav[i] = (float)((double)frames_raw[i] / 1E10);   // tools/...:208
+    write_wav_f32(out, wav, PBSO_SAMPLE_RATE, channels);
     if (!raw.empty()) {
         FILE *f = std::fopen(raw.c_str(), "wb");
         if (!f) die("cannot write " + raw);
-        std::fwrite(sound.data(), 4, sound.size(), f);
+        std::fwrite(frames_raw.data(), 4, frames_raw.size(), f);
         std::fclose(f);
     }
     std::printf("%d buffers (%.3f s of audio) in %.3f ms on the device -> %s\n", n_buffers,
