@@ -292,6 +292,34 @@ int pbso_enqueue_force_batch(pbso_engine *e, int n, const int *object_ids, const
  * Returns n, or PBSO_ERR_INVALID (ids / vertex ids out of range, object order) / PBSO_ERR_STATE (a script is pending). */
 int pbso_enqueue_vertex_hits(pbso_engine *e, int n, const int *object_ids, const int *vids, const double *vn,
                              const int64_t *not_before);
+/* A step's worth of CONTACT STROKES -- what the tool does while the mouse is dragged over the surface: a dummy message with
+ * sustainedForceStart (tools/real_time_modal_sound.cpp:754-776), one GetModalForceFace message per frame that replaces the
+ * spatial vector of the one live force (:1127-1160, modal_solver.h:190-204), a stop message -- as parallel arrays, object by
+ * object.  Entry i is exactly pbso_enqueue_force(e, object_ids[i], &m, not_before[i]) with m.force_type = force_type,
+ * m.data_kind = PBSO_DATA_FACE (vids / coords / vn from entry i of the arrays) or, with PBSO_STROKE_ZERO, PBSO_DATA_ZERO
+ * (setZero(N): the dummy start / stop messages; the entry's vids / coords / vn are ignored), and the two sustained flags from
+ * PBSO_STROKE_START / PBSO_STROKE_END; the entries are enqueued in array order.  flags == NULL: all 0.
+ * Everything else as pbso_enqueue_vertex_hits: object ids ascending, stamps ascending within an object, the arrays BORROWED
+ * until the next pbso_step returns, one script pending per engine (a vertex-hit script counts), any other enqueue call first
+ * moves a pending script into the queues with order kept, a full queue rejects an entry (counted in total_dropped_hits).
+ * That step takes the entries of an ELIGIBLE object straight into its descriptors: one record per object from the host, the
+ * per-buffer tables from a kernel on the device (kernels_stroke.hip).  Eligible: force_type autoregressive, a launch of at
+ * least two buffers (a one-buffer launch keeps the host path), nothing in the object's queue, no stamped call due inside the
+ * launch, listeners not enabled, and either no live force -- then the entries open with PBSO_STROKE_START -- or exactly the one
+ * sustained autoregressive force; an entry with PBSO_STROKE_END is the last one of the launch.  Every other object, and the
+ * entries that fall beyond the launch, go through the queue: the result is the same either way, pbso_stroke_stats says which
+ * way was taken.  Engines with time_chunks forced on take the fast path too.
+ * force_type: PBSO_POINT_FORCE or PBSO_AUTOREGRESSIVE_FORCE (a Gaussian needs a width per message: pbso_enqueue_force).
+ * Returns n, or PBSO_ERR_INVALID (ids / vertex ids out of range, object order, force_type) / PBSO_ERR_STATE. */
+#define PBSO_STROKE_START 1u
+#define PBSO_STROKE_END 2u
+#define PBSO_STROKE_ZERO 4u
+int pbso_enqueue_strokes(pbso_engine *e, int n, const int *object_ids, const int *vids /* [n][3] */,
+                         const double *coords /* [n][3] */, const double *vn /* [n][3] */, const int64_t *not_before,
+                         const unsigned char *flags /* [n] or NULL */, int force_type);
+/* totals since the engine was created: out[0] stroke entries taken straight into descriptors, out[1] entries that went through
+ * the queue, out[2] entries dropped (full queue), out[3] launches that ran the stroke kernel */
+int pbso_stroke_stats(pbso_engine *e, int64_t out[4]);
 /* ModalSolver::enqueueArprmMessageNoFail (modal_solver.h:382-393); 1-slot queue: a message that finds the slot taken waits in
  * the engine and enters when step() has taken the one before it (the reference's caller spins on try_enqueue meanwhile) */
 int pbso_enqueue_arprm(pbso_engine *e, int object_id, const double a[2], double sigma,

@@ -289,6 +289,24 @@ int pbso_enqueue_vertex_hits(pbso_engine *e, int n, const int *objs, const int *
     GUARD_END(e)
 }
 
+int pbso_enqueue_strokes(pbso_engine *e, int n, const int *objs, const int *vids, const double *coords, const double *vn,
+                         const int64_t *nb, const unsigned char *flags, int force_type) {
+    NEED(e);
+    if (n < 0 || (n && (!objs || !vids || !coords || !vn || !nb))) return PBSO_ERR_INVALID;
+    GUARD_BEGIN
+    return e->impl->enqueue_strokes(n, objs, vids, coords, vn, nb, flags, force_type);
+    GUARD_END(e)
+}
+
+int pbso_stroke_stats(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    if (!out) return PBSO_ERR_INVALID;
+    GUARD_BEGIN
+    e->impl->stroke_stats(out);
+    return PBSO_OK;
+    GUARD_END(e)
+}
+
 int pbso_enqueue_arprm(pbso_engine *e, int obj, const double a[2], double sigma, double mu, int64_t nb) {
     NEED(e);
     if (!a) return PBSO_ERR_INVALID;

@@ -25,8 +25,9 @@ namespace pbso {
 void PlanCtx::begin() {
     row_ptr.clear(); slot_idx.clear(); row_obj.clear(); stage_slot.clear(); chain_ptr.clear(); prow_obj.clear();
     tprof.clear(); prof_entries.clear(); prof_rows.clear(); stage.clear(); proj.clear(); proj_direct.clear(); ffat.clear();
-    forced.clear(); freed_this_plan.clear(); freed_ar.clear();
+    forced.clear(); freed_this_plan.clear(); freed_ar.clear(); strokes.clear();
     n_frows = n_prows = n_xfer = 0;
+    n_stroke_rows = n_stroke_proj = 0;
     chain_obj = -1;
     rc = 0;
     err.clear();
@@ -217,6 +218,15 @@ Engine::~Engine() {
             if (ev) (void)hipEventDestroy(ev);
     }
     if (prep_stream_) (void)hipStreamSynchronize(prep_stream_);
+    for (int i = 0; i < N_SETS; ++i) {
+        float ms = 0.f;
+        if (stroke_ev_live_[i] && hipEventElapsedTime(&ms, stroke_ev_[i][0], stroke_ev_[i][1]) == hipSuccess) { stroke_kernel_ms_ += ms; stroke_kernel_n_ += 1; }
+        for (int j = 0; j < 2; ++j)
+            if (stroke_ev_[i][j]) (void)hipEventDestroy(stroke_ev_[i][j]);
+    }
+    if (host_profile_ && stroke_kernel_n_ > 0)
+        std::fprintf(stderr, "pbso stroke kernel: %.4f ms per launch over %lld launches (HIP events)\n", stroke_kernel_ms_ / stroke_kernel_n_,
+                     (long long)stroke_kernel_n_);
     free_retired_blocks();
     d_ca_.release(); d_cb_.release(); d_sq_.release(); d_sd_.release(); d_ss_.release(); d_c3_.release(); d_gq_.release();
     d_shapes_.release(); d_shape_off_.release(); d_g32_.release(); d_g32_off_.release(); d_n_modes_.release(); d_geom_.release();
@@ -421,6 +431,9 @@ int Engine::init() {
     if (const char *v = std::getenv("PBSO_TIMELINE")) timeline_ = std::atoi(v) != 0;
     if (const char *v = std::getenv("PBSO_PREP_SPLIT")) prep_split_ = std::min(2, std::max(0, std::atoi(v)));
     host_profile_ = std::getenv("PBSO_HOST_PROFILE") != nullptr;
+    if (host_profile_)
+        for (int i = 0; i < N_SETS; ++i)
+            for (int j = 0; j < 2; ++j) HIPTRY(hipEventCreate(&stroke_ev_[i][j]));
     // which kernels run and how: per engine, from the descriptor (ABI 4); the environment only switches diagnostics on
     device_profiles_ = desc_.device_profiles >= 0;
     k2_rows_ = desc_.profile_kernel == 0;
@@ -1242,8 +1255,50 @@ int Engine::enqueue_vertex_hits(int n, const int *objs, const int *vids, const d
     }
     for (int o = 0; o < N; ++o)                       // objects without hits: an empty range at the running offset
         if (hit_off_[(size_t)o + 1] < hit_off_[o]) hit_off_[(size_t)o + 1] = hit_off_[o];
+    script_ = HitScript();
     script_.n = n; script_.objs = objs; script_.vids = vids; script_.vn = vn; script_.stamps = stamps;
     return n;
+}
+
+// pbso_enqueue_strokes: a step's stroke entries (face data or the dummy start / stop messages, with the sustained flags) as
+// borrowed parallel arrays, object by object -- the vertex-hit script's rules word for word.
+int Engine::enqueue_strokes(int n, const int *objs, const int *vids, const double *coords, const double *vn, const int64_t *stamps,
+                            const unsigned char *flags, int force_type) {
+    if (!finalized_) return fail(PBSO_ERR_STATE, "enqueue_strokes before finalize");
+    if (script_.n > 0) return fail(PBSO_ERR_STATE, "a hit script is already pending (one per step)");
+    if (force_type != PBSO_POINT_FORCE && force_type != PBSO_AUTOREGRESSIVE_FORCE)
+        return fail(PBSO_ERR_INVALID, "enqueue_strokes: force_type must be point or autoregressive (a Gaussian needs a width per message)");
+    if (n == 0) return 0;
+    const int N = (int)objs_.size();
+    hit_off_.assign((size_t)N + 1, 0);
+    int prev = 0;
+    for (int i = 0; i < n; ++i) {
+        const int o = objs[i];
+        if (o < prev || o >= N) return fail(PBSO_ERR_INVALID, "enqueue_strokes: object ids must be valid and ascending");
+        if (!(flags && (flags[i] & STROKE_ZERO))) {
+            const int n_dof = objs_[o].n_dof;
+            if (!n_dof) return fail(PBSO_ERR_INVALID, "object has no mode shapes for on-device projection");
+            for (int j = 0; j < 3; ++j) {
+                const int v = vids[3 * (size_t)i + j];
+                if (v < 0 || v >= n_dof / 3) return fail(PBSO_ERR_INVALID, "vertex id out of range");
+            }
+        }
+        prev = o;
+        hit_off_[(size_t)o + 1] = i + 1;
+    }
+    for (int o = 0; o < N; ++o)
+        if (hit_off_[(size_t)o + 1] < hit_off_[o]) hit_off_[(size_t)o + 1] = hit_off_[o];
+    script_ = HitScript();
+    script_.n = n; script_.objs = objs; script_.vids = vids; script_.vn = vn; script_.stamps = stamps;
+    script_.strokes = true; script_.coords = coords; script_.flags = flags; script_.force_type = force_type;
+    return n;
+}
+
+void Engine::stroke_stats(int64_t out[4]) const {
+    out[0] = stroke_direct_.load();
+    out[1] = stroke_queued_.load();
+    out[2] = stroke_dropped_.load();
+    out[3] = tot_stroke_launches_;
 }
 
 // hits h0 .. h1 - 1 of the script (all of object oi) enter the object's queue exactly as pbso_enqueue_force would put them: a
@@ -1252,6 +1307,35 @@ int Engine::enqueue_vertex_hits(int n, const int *objs, const int *vids, const d
 int Engine::script_to_queue(int oi, int h0, int h1, const char **why) {
     (void)why;
     Object &o = objs_[oi];
+    if (script_.strokes) {
+        // entry h as pbso_enqueue_force would queue it (enqueue_force_impl: the same fields, the same heap block for a face)
+        for (int h = h0; h < h1; ++h) {
+            if (o.force_q.size() >= 1023) { dropped_hits_.fetch_add(h1 - h); stroke_dropped_.fetch_add(h1 - h); break; }
+            const int fl = script_.flags ? script_.flags[h] : 0;
+            HostForceMsg m;
+            m.force_type = (int8_t)script_.force_type;
+            m.sustained_start = (fl & STROKE_START) != 0;
+            m.sustained_end = (fl & STROKE_END) != 0;
+            m.not_before = script_.stamps[h];
+            if (fl & STROKE_ZERO) {
+                m.data_kind = PBSO_DATA_ZERO;
+            } else {
+                m.data_kind = PBSO_DATA_FACE;
+                m.ext = (MsgExt *)std::malloc(sizeof(MsgExt));
+                m.ext->gaussian_width_us = 0.0;
+                m.ext->n_data = 0;
+                for (int j = 0; j < 3; ++j) {
+                    m.vids[j] = script_.vids[3 * (size_t)h + j];
+                    m.vn[j] = script_.vn[3 * (size_t)h + j];
+                    m.ext->coords[j] = script_.coords[3 * (size_t)h + j];
+                }
+            }
+            if (!o.force_q.empty()) m.not_before = std::max(m.not_before, o.force_q.back().not_before);
+            o.force_q.push_back(std::move(m));
+            stroke_queued_.fetch_add(1);
+        }
+        return PBSO_OK;
+    }
     for (int h = h0; h < h1; ++h) {
         if (o.force_q.size() >= 1023) { dropped_hits_.fetch_add(h1 - h); break; }
         HostForceMsg m;
@@ -1311,6 +1395,136 @@ int Engine::consume_script(PlanCtx &c, int oi, int nb) {
     const char *why = "";
     int rc = script_to_queue(oi, h, h1, &why);       // what is left: beyond this launch, or the object is busy
     if (rc != PBSO_OK) return cfail(c, rc, why);
+    return PBSO_OK;
+}
+
+// Planner, before an object's buffers are planned: its share of a pending STROKE script.  The object is eligible when taking the
+// entries out of the arrays cannot be told from the queue: nothing queued, no stamped call due inside the launch (AR parameters
+// already in the 1-slot queue are taken by the first dense row, modal_solver.h:226-236), no transfer work, and either no live force
+// -- then the entries that land in this launch open with sustainedForceStart -- or exactly the one sustained AR force.  The shapes
+// taken are  [start] data* [end]  with an AutoregressiveForce: the scraping of tools/real_time_modal_sound.cpp:754-776, 1127-1160.
+// For those the host reserves ranges and writes one StrokeRec; stroke_expand_kernel does the rest (kernels_stroke.hip).  Anything
+// else -- a PointForce, a second start, a stroke interrupted by clearAllForces (sustained with an empty list: plan_object reports
+// PBSO_ERR_ASSERT for it), listeners enabled, a launch of one buffer -- and the entries beyond the launch go through the queue.
+int Engine::consume_strokes(PlanCtx &c, int oi, int nb, bool *taken) {
+    *taken = false;
+    if (script_.n <= 0) return PBSO_OK;
+    const int h0 = hit_off_[oi], h1 = hit_off_[(size_t)oi + 1];
+    if (h0 >= h1) return PBSO_OK;
+    Object &o = objs_[oi];
+    const char *why = "";
+    const int64_t horizon = buffers_done_ + nb;
+    bool ok = device_profiles_ && nb >= 2 && nb <= STROKE_MAX_BUFFERS && script_.force_type == PBSO_AUTOREGRESSIVE_FORCE &&
+              o.force_q.empty() && !o.trans_full &&
+              !(o.path_left() && o.path[o.path_head].stamp < horizon) && (n_dump_ == 0 || dump_row_[oi] < 0);
+    if (ok && o.sustained)
+        ok = o.active.size() == 1 && o.active.front().force_type == PBSO_AUTOREGRESSIVE_FORCE && o.active.front().ar_state >= 0 &&
+             o.active.front().slot >= 0;
+    else if (ok)
+        ok = o.active.empty();
+    if (ok) {
+        // calls stamped for the launch's first buffer or earlier take effect there (plan_object's first lines): AR parameters enter
+        // the 1-slot queue, setUseTransfer switches; a listener move, or anything stamped later inside the launch, needs the planner
+        size_t due = 0;
+        bool full = o.arprm_full, use_t = o.use_transfer;
+        while (due < o.pending.size() && o.pending[due].not_before <= buffers_done_) {
+            const TimedEvent &ev = o.pending[due];
+            if (ev.kind == TimedEvent::ARPRM && !full) full = true;
+            else if (ev.kind == TimedEvent::USE_TRANSFER) use_t = ev.flag != 0;
+            else break;
+            ++due;
+        }
+        ok = (due == o.pending.size() || o.pending[due].not_before >= horizon) && !(!use_t && o.latest_row != XFER_UNIT);
+        if (ok) {
+            for (size_t i = 0; i < due; ++i) {
+                const TimedEvent &ev = o.pending.front();
+                if (ev.kind == TimedEvent::ARPRM) { o.arprm_full = true; std::memcpy(o.arprm, ev.v, sizeof(o.arprm)); }
+                else o.use_transfer = ev.flag != 0;
+                o.pending.pop_front();
+            }
+        }
+    }
+    // the entries that land inside the launch, one per buffer; their flags decide
+    int K = 0, n_face = 0, b_first = 0, b_last = -1;
+    bool has_end = false;
+    if (ok) {
+        int next_b = 0;
+        for (int h = h0; h < h1; ++h) {
+            const int64_t rel = script_.stamps[h] - buffers_done_;
+            const int b = (int)std::max<int64_t>(std::min<int64_t>(rel, nb), next_b);
+            if (b >= nb) break;
+            const int fl = script_.flags ? script_.flags[h] : 0;
+            const bool first = h == h0;
+            if (has_end || ((fl & STROKE_START) != 0) != (first && !o.sustained) || ((fl & STROKE_START) && (fl & STROKE_END))) { ok = false; break; }
+            has_end = (fl & STROKE_END) != 0;
+            if (!(fl & STROKE_ZERO)) ++n_face;
+            if (first) b_first = b;
+            b_last = b;
+            next_b = b + 1;
+            ++K;
+        }
+        ok = ok && K > 0;
+    }
+    if (!ok) {
+        int rc = script_to_queue(oi, h0, h1, &why);
+        return rc != PBSO_OK ? cfail(c, rc, why) : PBSO_OK;
+    }
+    // ---- one record
+    StrokeRec r;
+    std::memset(&r, 0, sizeof(r));
+    r.obj = oi;
+    r.e0 = h0;
+    r.n_ent = K;
+    if (K > o.stroke_cap) {
+        // (a larger pair of ranges; the old ones are not reused -- the row in force may still live there)
+        o.stroke_cap = (std::max(K, o.stroke_cap + o.stroke_cap / 2) + 7) & ~7;
+        o.stroke_base = (int)n_slots_.fetch_add((size_t)2 * o.stroke_cap);
+        o.stroke_half = 0;
+    }
+    r.slot0 = o.stroke_base + o.stroke_half * o.stroke_cap;
+    o.stroke_half ^= 1;
+    r.sustained0 = o.sustained ? 1 : 0;
+    if (!o.sustained) {                                    // sustainedForceStart (modal_solver.h:190-194): a fresh force
+        ActiveForce af;
+        af.force_type = PBSO_AUTOREGRESSIVE_FORCE;
+        af.force = ForceProfile::make(PBSO_AUTOREGRESSIVE_FORCE, 0.0, rate_);
+        if (!c.free_ar.empty()) { af.ar_state = c.free_ar.back(); c.free_ar.pop_back(); }
+        else af.ar_state = (int)n_ar_states_.fetch_add(1);
+        r.flags0 |= 1;
+        o.active.push_back(af);
+        o.sustained = true;
+        r.carry_slot = -1;
+    } else {
+        r.carry_slot = o.active.front().slot;
+        free_slot(c, o.active.front());                    // replaced by the first entry (:197-200)
+    }
+    ActiveForce &af = o.active.front();
+    af.slot = r.slot0 + K - 1;
+    af.slot_pinned = true;
+    r.ar_state = af.ar_state;
+    const int first_dense = r.sustained0 ? 0 : b_first, end_dense = has_end ? b_last : nb;
+    r.n_dense = end_dense - first_dense;
+    if (r.n_dense > 0 && o.arprm_full) {                   // :226-236, at the first profile row
+        o.arprm_full = false;
+        r.flags0 |= 2;
+        std::memcpy(r.arprm, o.arprm, sizeof(r.arprm));
+    }
+    if (r.n_dense <= 0) r.flags0 = 0;                      // (start and end within ... never: start + end in one launch needs two entries, one buffer apart)
+    r.row0 = c.n_stroke_rows;
+    r.proj0 = c.n_stroke_proj;
+    r.stream = -1;
+    c.n_stroke_rows += r.n_dense;
+    c.n_stroke_proj += n_face;
+    c.strokes.push_back(r);
+    if (has_end) {                                         // :201-204
+        for (ActiveForce &x : o.active) release(c, x);
+        o.active.clear();
+        o.sustained = false;
+    }
+    stroke_direct_.fetch_add(K);
+    int rc = script_to_queue(oi, h0 + K, h1, &why);        // what falls beyond this launch
+    if (rc != PBSO_OK) return cfail(c, rc, why);
+    *taken = true;
     return PBSO_OK;
 }
 
@@ -1524,7 +1738,7 @@ int Engine::set_use_transfer(int obj, int use, int64_t not_before) {
 }
 
 void Engine::release(PlanCtx &c, ActiveForce &af) {
-    if (af.slot >= 0) c.freed_this_plan.push_back(af.slot);      // (negative: an on-the-fly projection, no pool row)
+    free_slot(c, af);                                            // (negative: an on-the-fly projection, no pool row)
     if (af.ar_state >= 0) c.freed_ar.push_back(af.ar_state);
     af.ar_state = -1;
 }
@@ -1670,8 +1884,9 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
             if (o.active.empty())
                 return cfail(c, PBSO_ERR_ASSERT, "sustained force list is empty (reference dereferences begin() of an empty list)");
             if (o.active.front().slot != slot) {
-                c.freed_this_plan.push_back(o.active.front().slot);
+                free_slot(c, o.active.front());
                 o.active.front().slot = slot;
+                o.active.front().slot_pinned = false;
                 slot_used = true;
             }
         }
@@ -1860,8 +2075,10 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
 int Engine::plan_object_span(PlanCtx &c, int oi, int nb) {
     Object &o = objs_[oi];
     {
-        int rc = consume_script(c, oi, nb);
-        if (rc == PBSO_OK) rc = consume_path(c, oi, nb);
+        bool taken = false;
+        int rc = script_.strokes ? consume_strokes(c, oi, nb, &taken) : consume_script(c, oi, nb);
+        if (rc != PBSO_OK || taken) return rc;
+        rc = consume_path(c, oi, nb);
         if (rc != PBSO_OK) return rc;
     }
     int b = 0;
@@ -2029,6 +2246,22 @@ int Engine::plan(int nb) {
         c.free_slots.insert(c.free_slots.end(), c.freed_this_plan.begin(), c.freed_this_plan.end());
         c.free_ar.insert(c.free_ar.end(), c.freed_ar.begin(), c.freed_ar.end());
     }
+    // stroke records: their rows and events are numbered behind everything the host planned, context after context
+    stroke_recs_.clear();
+    n_stroke_rows_ = n_stroke_proj_ = 0;
+    for (int t = 0; t < T; ++t) {
+        PlanCtx &c = ctx_[t];
+        for (StrokeRec r : c.strokes) {
+            r.row0 += n_stroke_rows_;
+            r.proj0 += n_stroke_proj_;
+            if (r.n_dense > 0) chain_ptr_.push_back((int)prof_rows_.size() + r.row0);
+            stroke_recs_.push_back(r);
+        }
+        n_stroke_rows_ += c.n_stroke_rows;
+        n_stroke_proj_ += c.n_stroke_proj;
+    }
+    n_frows_ += n_stroke_rows_;
+    n_prows_ += n_stroke_rows_;
     build_ar_tables();
     const auto tp3 = std::chrono::steady_clock::now();
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -2049,7 +2282,7 @@ int Engine::plan(int nb) {
 void Engine::build_ar_tables() {
     ar_streams_.clear(); ar_uses_.clear(); seg_stream_.clear();
     ar_max_segs_ = 0;
-    k2_rows_launch_ = device_profiles_ && k2_rows_ && !ar_serial_ && B_ >= 3 && !prof_rows_.empty();
+    k2_rows_launch_ = device_profiles_ && k2_rows_ && !ar_serial_ && B_ >= 3 && (!prof_rows_.empty() || n_stroke_rows_ > 0);
     if (!k2_rows_launch_) return;
     const size_t n_states = n_ar_states_.load();
     if (ar_stream_of_state_.size() < n_states) ar_stream_of_state_.resize(n_states, -1);
@@ -2082,12 +2315,25 @@ void Engine::build_ar_tables() {
         ar_last_use_[(size_t)si] = (int)ar_uses_.size();
         ar_uses_.push_back(U);
     }
+    // the forces of stroke records: one stream each, its uses the record's dense rows in order (stroke_expand_kernel writes them)
+    const size_t n_host_streams = ar_streams_.size();
+    for (StrokeRec &r : stroke_recs_) {
+        r.stream = -1;
+        if (!k2_rows_launch_ || r.n_dense <= 0) continue;
+        r.stream = (int)ar_streams_.size();
+        ArStream S;
+        std::memset(&S, 0, sizeof(S));
+        S.state = r.ar_state;
+        S.reset = (r.flags0 & 1) ? 1 : 0;
+        S.n_uses = r.n_dense;
+        ar_streams_.push_back(S);
+    }
     int use0 = 0, seg0 = 0;
     for (size_t si = 0; si < ar_streams_.size(); ++si) {
         ArStream &S = ar_streams_[si];
         ar_stream_of_state_[(size_t)S.state] = -1;
         if (!k2_rows_launch_) continue;
-        ar_uses_[(size_t)ar_last_use_[si]].last = 1;
+        if (si < n_host_streams) ar_uses_[(size_t)ar_last_use_[si]].last = 1;
         S.use0 = use0;
         use0 += S.n_uses;
         const double pairs = 0.5 * ((double)S.n_uses * B_ + 1.0);
@@ -2099,7 +2345,10 @@ void Engine::build_ar_tables() {
         seg_stream_.insert(seg_stream_.end(), (size_t)S.n_seg, (int)si);
     }
     if (ar_max_segs_ > 8192) k2_rows_launch_ = false;     // (the prefix table of a stream's segments lives in LDS: > 8 M candidates per force and launch)
-    if (!k2_rows_launch_) { ar_streams_.clear(); ar_uses_.clear(); seg_stream_.clear(); }
+    if (!k2_rows_launch_) {
+        ar_streams_.clear(); ar_uses_.clear(); seg_stream_.clear();
+        for (StrokeRec &r : stroke_recs_) r.stream = -1;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2251,6 +2500,14 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
         if (submit_->error(&why)) return fail(PBSO_ERR_HIP, "a launch of an earlier step failed on the submitting thread: " + why);
     }
     HIPTRY(hipEventSynchronize(ev_set_[cur_set_]));      // ... and this set's previous uploads are done
+    if (stroke_ev_live_[cur_set_]) {                     // PBSO_HOST_PROFILE=1: the stroke kernel of the launch that last used this set
+        float ms = 0.f;
+        HIPTRY(hipEventSynchronize(stroke_ev_[cur_set_][1]));
+        HIPTRY(hipEventElapsedTime(&ms, stroke_ev_[cur_set_][0], stroke_ev_[cur_set_][1]));
+        stroke_kernel_ms_ += ms;
+        stroke_kernel_n_ += 1;
+        stroke_ev_live_[cur_set_] = false;
+    }
 
     const auto t0 = std::chrono::steady_clock::now();
     hprof_[0] += std::chrono::duration<double, std::milli>(t0 - tw0).count();
@@ -2272,7 +2529,10 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
         }
     }
     const int n_chains = (int)chain_ptr_.size();
-    chain_ptr_.push_back((int)prof_rows_.size());
+    const int n_srows = n_stroke_rows_, n_srecs = (int)stroke_recs_.size();
+    const int n_prof_rows = (int)prof_rows_.size() + n_srows;          // (stroke rows: written on the device, behind the host's)
+    const int n_ar_uses = (int)ar_uses_.size() + (k2_rows_launch_ ? n_srows : 0);
+    chain_ptr_.push_back(n_prof_rows);
     last_plan_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     const auto tsub0 = std::chrono::steady_clock::now();
 
@@ -2367,19 +2627,26 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
             proj_.clear();
         }
     }
+    const int n_proj = (int)proj_.size() + n_stroke_proj_;      // (behind the fusion above, which may have emptied proj_)
     size_t off = ps.front_bytes;
     auto place = [&](size_t bytes) { const size_t o = off; off += arena_align(bytes); return o; };
-    const size_t o_row_ptr = place(row_ptr_.size() * sizeof(int)), o_slot_idx = place(slot_idx_.size() * sizeof(int));
-    const size_t o_row_obj = place(row_obj_.size() * sizeof(int));
-    const size_t o_prow_obj = place(prow_obj_.size() * sizeof(int));
-    const size_t o_pent = place(device_profiles_ ? prof_entries_.size() * sizeof(ProfEntry) : 0);
-    const size_t o_prow = place(device_profiles_ ? prof_rows_.size() * sizeof(ProfRow) : 0);
+    // (every table with stroke rows: room for them behind the host's part; stroke_expand_kernel fills it in the device copy)
+    const size_t o_row_ptr = place((row_ptr_.size() + n_srows) * sizeof(int)), o_slot_idx = place((slot_idx_.size() + n_srows) * sizeof(int));
+    const size_t o_row_obj = place((row_obj_.size() + n_srows) * sizeof(int));
+    const size_t o_prow_obj = place((prow_obj_.size() + n_srows) * sizeof(int));
+    const size_t o_pent = place(device_profiles_ ? (prof_entries_.size() + n_srows) * sizeof(ProfEntry) : 0);
+    const size_t o_prow = place(device_profiles_ ? (size_t)n_prof_rows * sizeof(ProfRow) : 0);
     const size_t o_chain = place(device_profiles_ ? chain_ptr_.size() * sizeof(int) : 0);
-    const size_t o_aruse = place(ar_uses_.size() * sizeof(ArUse)), o_arstream = place(ar_streams_.size() * sizeof(ArStream));
+    const size_t o_aruse = place((size_t)n_ar_uses * sizeof(ArUse)), o_arstream = place(ar_streams_.size() * sizeof(ArStream));
     const size_t o_arseg = place(seg_stream_.size() * sizeof(int));
     const size_t o_tprof = place(device_profiles_ ? 0 : tprof_.size() * sizeof(float));
     const size_t o_stage = place(stage_.size() * sizeof(double)), o_stage_slot = place(stage_slot_.size() * sizeof(int));
-    const size_t o_proj = place(proj_.size() * sizeof(ProjectEvent)), o_projd = place(proj_direct_.size() * sizeof(ProjectEvent));
+    const size_t o_proj = place((size_t)n_proj * sizeof(ProjectEvent)), o_projd = place(proj_direct_.size() * sizeof(ProjectEvent));
+    // the stroke records and the part of the caller's arrays they refer to, as given (the arrays are borrowed only until the step returns)
+    const int s_lo = n_srecs ? stroke_recs_.front().e0 : 0, s_n = n_srecs ? stroke_recs_.back().e0 + stroke_recs_.back().n_ent - s_lo : 0;
+    const size_t o_srec = place((size_t)n_srecs * sizeof(StrokeRec)), o_sstamp = place((size_t)s_n * sizeof(int64_t));
+    const size_t o_svids = place((size_t)s_n * 3 * sizeof(int)), o_scoords = place((size_t)s_n * 3 * sizeof(double));
+    const size_t o_svn = place((size_t)s_n * 3 * sizeof(double)), o_sflags = place(script_.flags ? (size_t)s_n : 0);
     // the listener events as runs of one object each (the planner lists them object by object): one geometry read per (run, mode)
     // (events of objects whose modes share one map geometry first: they go to the kernel that locates a position once per event)
     int n_ffat_sh = 0;
@@ -2414,7 +2681,7 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
         put(o_arstream, ar_streams_.data(), ar_streams_.size() * sizeof(ArStream));
         put(o_arseg, seg_stream_.data(), seg_stream_.size() * sizeof(int));
         if (k2_rows_launch_) {
-            const size_t ns = std::max<size_t>(1, ar_streams_.size()), nu = std::max<size_t>(1, ar_uses_.size());
+            const size_t ns = std::max<size_t>(1, ar_streams_.size()), nu = std::max<size_t>(1, (size_t)n_ar_uses);
             const size_t ng = std::max<size_t>(1, seg_stream_.size());
             GROWTRY(d_ar_snaps_, ns, false, sp);
             GROWTRY(d_ar_fins_, ns, false, sp);
@@ -2433,6 +2700,15 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
     put(o_stage_slot, stage_slot_.data(), stage_slot_.size() * sizeof(int));
     put(o_proj, proj_.data(), proj_.size() * sizeof(ProjectEvent));
     put(o_projd, proj_direct_.data(), proj_direct_.size() * sizeof(ProjectEvent));
+    if (n_srecs) {
+        StrokeRec *hr = reinterpret_cast<StrokeRec *>(ha + o_srec);
+        for (int i = 0; i < n_srecs; ++i) { hr[i] = stroke_recs_[(size_t)i]; hr[i].e0 -= s_lo; }
+        put(o_sstamp, script_.stamps + s_lo, (size_t)s_n * sizeof(int64_t));
+        put(o_svids, script_.vids + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(int));
+        put(o_scoords, script_.coords + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(double));
+        put(o_svn, script_.vn + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(double));
+        if (script_.flags) put(o_sflags, script_.flags + s_lo, (size_t)s_n);
+    }
     put(o_ffat, ffat_.data(), ffat_.size() * sizeof(FfatEvent));
     put(o_ffat_runs, ffat_runs_.data(), ffat_runs_.size() * sizeof(FfatRun));
     put(o_copy, cp.data(), cp.size() * sizeof(int));
@@ -2470,6 +2746,43 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
     evq.h_copy = host_ms();
     const auto tsub1 = std::chrono::steady_clock::now();
     unsigned char *da = ps.d_arena.p;
+    if (n_srecs) {
+        // stroke records -> descriptors, events, profile rows: behind the upload (it overwrites the eligible objects' default rows in
+        // the device copy), in front of everything that reads the plan
+        StrokeTables st;
+        std::memset(&st, 0, sizeof(st));
+        st.recs = reinterpret_cast<const StrokeRec *>(da + o_srec);
+        st.stamps = reinterpret_cast<const int64_t *>(da + o_sstamp);
+        st.vids = reinterpret_cast<const int32_t *>(da + o_svids);
+        st.coords = reinterpret_cast<const double *>(da + o_scoords);
+        st.vn = reinterpret_cast<const double *>(da + o_svn);
+        st.flags = script_.flags ? da + o_sflags : nullptr;
+        st.buffers_done = buffers_done_;
+        st.nb = nb;
+        st.tile_mask = n_tiles_ >= 32 ? 0xFFFFFFFFu : ((1u << n_tiles_) - 1u);
+        st.desc = reinterpret_cast<BufDesc *>(da);
+        st.row_ptr = reinterpret_cast<int32_t *>(da + o_row_ptr);
+        st.slot_idx = reinterpret_cast<int32_t *>(da + o_slot_idx);
+        st.row_obj = reinterpret_cast<int32_t *>(da + o_row_obj);
+        st.prow_obj = reinterpret_cast<int32_t *>(da + o_prow_obj);
+        st.prof_rows = reinterpret_cast<ProfRow *>(da + o_prow);
+        st.prof_entries = reinterpret_cast<ProfEntry *>(da + o_pent);
+        st.ar_uses = k2_rows_launch_ ? reinterpret_cast<ArUse *>(da + o_aruse) : nullptr;
+        st.proj = reinterpret_cast<ProjectEvent *>(da + o_proj);
+        st.slots = d_slots_.p;
+        st.frow_base = n_frows - n_srows;
+        st.prow_base = n_prows_ - n_srows;
+        st.sidx_base = (int)slot_idx_.size();
+        st.entry_base = (int)prof_entries_.size();
+        st.prof_row_base = (int)prof_rows_.size();
+        st.use_base = (int)ar_uses_.size();
+        st.proj_base = (int)proj_.size();
+        st.m_pad = m_pad_;
+        if (host_profile_ && stroke_ev_[cur_set_][0]) QHIP(hipEventRecord, stroke_ev_[cur_set_][0], sp);
+        QLAUNCH(launch_stroke_expand, st, n_srecs, sp);
+        if (host_profile_ && stroke_ev_[cur_set_][0]) { QHIP(hipEventRecord, stroke_ev_[cur_set_][1], sp); stroke_ev_live_[cur_set_] = true; }
+        tot_stroke_launches_ += 1;
+    }
     const BufDesc *d_desc = reinterpret_cast<const BufDesc *>(da);
     const int *d_xfer_init = reinterpret_cast<const int *>(da + ps.off_xfer_init);
     const int *d_row_ptr = reinterpret_cast<const int *>(da + o_row_ptr), *d_slot_idx = reinterpret_cast<const int *>(da + o_slot_idx);
@@ -2543,24 +2856,24 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
     const bool rows_and_combine = device_profiles_ && k2_rows_launch_ && fuse_combine && sa == sp && !prof_rows_.empty() && n_frows > 0 &&
                                   fuse_short_ && !ar_uses_.empty() && ar_uses_.size() == ar_streams_.size();
     if (rows_and_combine)
-        QLAUNCH(launch_force_rows_combine, d_prow, (int)prof_rows_.size(), d_pent, reinterpret_cast<const ArUse *>(da + o_aruse),
+        QLAUNCH(launch_force_rows_combine, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse),
                                             reinterpret_cast<const ArStream *>(da + o_arstream), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p,
                                             d_ar_vnorm_.p, d_ar_vstate_.p, d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p,
                                             ps.d_tprof.p, B_, b_pad_, b_pad_, d_row_ptr, d_slot_idx, d_row_obj, n_frows, d_slots_.p, d_c3_.p,
                                             grows.p, d_projd, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, m_pad_, (int)proj_direct_.size(),
                                             d_stage, d_stage_slot, sp);
     else if (device_profiles_ && k2_rows_launch_)
-        QLAUNCH(launch_force_rows, d_prow, (int)prof_rows_.size(), d_pent, reinterpret_cast<const ArUse *>(da + o_aruse), (int)ar_uses_.size(),
+        QLAUNCH(launch_force_rows, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse), n_ar_uses,
                                     reinterpret_cast<const ArStream *>(da + o_arstream), reinterpret_cast<const int *>(da + o_arseg),
                                     (int)seg_stream_.size(), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p, d_ar_vnorm_.p, d_ar_vstate_.p,
                                     d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p, ps.d_tprof.p, B_, b_pad_, b_pad_,
                                     /* every AR force adds its samples once (a launch of one buffer): one launch instead of three */
-                                    fuse_short_ && !ar_uses_.empty() && ar_uses_.size() == ar_streams_.size(), sp);
+                                    fuse_short_ && n_ar_uses > 0 && (size_t)n_ar_uses == ar_streams_.size(), sp);
     else if (device_profiles_)
         QLAUNCH(launch_force_profiles, d_chain, n_chains, d_prow, d_pent, d_arstate_.p, ps.d_tprof.p, B_, b_pad_, ar_serial_ ? 1 : 0, k2_prio_, sp);
     if (evq.has_k2) QHIP(hipEventRecord, evq.f1, sp);
     if (!fuse_combine) QLAUNCH(launch_scatter_rows, d_stage, d_stage_slot, (int)stage_slot_.size(), d_slots_.p, m_pad_, sa);
-    QLAUNCH(launch_modal_project, d_proj, (int)proj_.size(), d_shapes_.p, d_shape_off_.p, d_n_modes_.p, d_slots_.p, m_pad_, sa);
+    QLAUNCH(launch_modal_project, d_proj, n_proj, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, d_slots_.p, m_pad_, sa);
     // (a few events: one thread per (event, mode); listener paths -- many events per object -- by runs)
     if (n_ffat_sh > 0)
         QLAUNCH(launch_ffat_lookup_shared, d_ffat, n_ffat_sh, d_ffat_shared_.p, d_geom_.p, d_geom_off_.p, d_n_modes_.p, d_ffat_k_.p,

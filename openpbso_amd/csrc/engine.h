@@ -113,6 +113,7 @@ struct ActiveForce {                                     // one entry of _active
     int slot = -1;                                       // row of the device data-slot pool
     int ar_state = -1;                                   // device ArState slot of an AutoregressiveForce
     int force_type = PBSO_POINT_FORCE;
+    bool slot_pinned = false;                            // the row belongs to the object's stroke ranges: never returned to the pool
     ForceProfile force;
 };
 
@@ -151,6 +152,9 @@ struct Object {
     std::vector<PathEv> path;
     size_t path_head = 0;
     bool path_left() const { return path_head < path.size(); }
+    // data rows of stroke scripts taken straight into descriptors (Engine::consume_strokes): two ranges of stroke_cap rows of the
+    // slot pool, used in turn -- the row a launch leaves in force lives in the other half while the next launch fills its own
+    int stroke_base = -1, stroke_cap = 0, stroke_half = 0;
 };
 
 // Everything one planning pass over a contiguous range of objects produces.  The planner runs one
@@ -168,6 +172,9 @@ struct PlanCtx {
     std::vector<FfatEvent> ffat;
     std::vector<BufDesc *> forced;                       // descriptors holding context-local frow / prow numbers
     std::vector<int> free_slots, freed_this_plan, free_ar, freed_ar;     // this context's share of the slot / AR-state pools
+    // stroke scripts: one record per object taken straight into descriptors (row0 / proj0 count within this context)
+    std::vector<StrokeRec> strokes;
+    int n_stroke_rows = 0, n_stroke_proj = 0;
     std::vector<double> tbuf;
     int t_extent = 0, n_frows = 0, n_prows = 0, n_xfer = 0, xfer_base = 0, chain_obj = -1;
     int rc = 0;
@@ -189,6 +196,9 @@ public:
     int enqueue_force(int obj, const pbso_force_msg &m, int64_t not_before);
     int enqueue_force_batch(int n, const int *objs, const pbso_force_msg *msgs, const int64_t *stamps, unsigned char *accepted);
     int enqueue_vertex_hits(int n, const int *objs, const int *vids, const double *vn, const int64_t *stamps);
+    int enqueue_strokes(int n, const int *objs, const int *vids, const double *coords, const double *vn, const int64_t *stamps,
+                        const unsigned char *flags, int force_type);
+    void stroke_stats(int64_t out[4]) const;
     int enqueue_arprm(int obj, const double a[2], double sigma, double mu, int64_t not_before);
     int arprm_pending(int obj);
     int compute_transfer(int obj, const double pos[3], int64_t not_before);
@@ -237,12 +247,34 @@ private:
     int plan_object_span(PlanCtx &c, int o, int nb);
     // the borrowed script of plain vertex hits (pbso_enqueue_vertex_hits): arrays of the caller, valid until the next step
     // has planned; hit_off_[o] .. hit_off_[o + 1] are object o's hits
-    struct HitScript { int n = 0; const int *objs = nullptr, *vids = nullptr; const double *vn = nullptr; const int64_t *stamps = nullptr; } script_;
+    // (a stroke script -- pbso_enqueue_strokes -- is the same thing with three vertices, barycentric coordinates and flags per entry)
+    struct HitScript {
+        int n = 0;
+        const int *objs = nullptr, *vids = nullptr;
+        const double *vn = nullptr;
+        const int64_t *stamps = nullptr;
+        bool strokes = false;
+        const double *coords = nullptr;
+        const unsigned char *flags = nullptr;
+        int force_type = PBSO_POINT_FORCE;
+    } script_;
     std::vector<int> hit_off_;
     std::atomic<int64_t> dropped_hits_{0};               // hits of a script that found their object's queue full (rejected as try_enqueue would)
     int script_to_queue(int oi, int h0, int h1, const char **why);     // hits h0 .. h1 - 1 of object oi enter its queue, in order
     int flush_script();                                                 // all of it (another enqueue call came before the step)
     int consume_script(PlanCtx &c, int oi, int nb);                     // planner: the object's hits of this launch
+    // planner: the object's stroke entries of this launch; *taken: they went straight into a StrokeRec and the object's buffers
+    // of this launch are planned (kernels_stroke.hip).  One-buffer launches keep the host path (their combine reads the host's lists).
+    int consume_strokes(PlanCtx &c, int oi, int nb, bool *taken);
+    void free_slot(PlanCtx &c, const ActiveForce &af) { if (af.slot >= 0 && !af.slot_pinned) c.freed_this_plan.push_back(af.slot); }
+    std::vector<StrokeRec> stroke_recs_;                 // the launch's records, rows and events numbered over all contexts
+    int n_stroke_rows_ = 0, n_stroke_proj_ = 0;
+    int64_t tot_stroke_launches_ = 0;
+    hipEvent_t stroke_ev_[3][2] = {};                    // PBSO_HOST_PROFILE=1: around the stroke kernel, per plan set
+    bool stroke_ev_live_[3] = {false, false, false};
+    double stroke_kernel_ms_ = 0;
+    int64_t stroke_kernel_n_ = 0;
+    std::atomic<int64_t> stroke_direct_{0}, stroke_queued_{0}, stroke_dropped_{0};      // entries, by the way they took
     // the listener's twin of the hit script (Object::path)
     void path_to_pending(Object &o, int64_t before);     // positions stamped below `before` enter the pending list, in order
     int consume_path(PlanCtx &c, int oi, int nb);

@@ -246,6 +246,48 @@ int launch_force_rows_combine(const ProfRow *rows, int n_rows, const ProfEntry *
                               float *grows, const struct ProjectEvent *direct, const double *shapes, const long long *shape_off, const int *n_modes,
                               int m_pad, int n_events, const double *stage, const int *stage_slot, hipStream_t stream);
 
+// ---- stroke scripts (pbso_enqueue_strokes; kernels_stroke.hip): the planner writes ONE record per eligible object of a launch
+// and uploads the caller's arrays as they are; stroke_expand_kernel builds, on the device, what the planner otherwise writes
+// per (object, buffer): BufDesc rows, ProjectEvents, ProfRow / ProfEntry, row_ptr / slot_idx / row_obj / prow_obj and the
+// row-parallel K2's ArUse records.  Every dense row of a stroke has exactly one data slot, one profile entry and one AR use,
+// so one running index `row0` places all of them behind the rows the host planned (StrokeTables holds those counts).
+constexpr int STROKE_START = 1, STROKE_END = 2, STROKE_ZERO = 4;      // pbso_enqueue_strokes flags
+constexpr int STROKE_MAX_BUFFERS = 4096;                             // buffers per launch the kernel's LDS table covers
+struct StrokeRec {
+    int32_t obj;
+    int32_t e0, n_ent;       // entries e0 .. e0 + n_ent - 1 of the script land in this launch (one per buffer, modal_solver.h:184)
+    int32_t slot0;           // entry k's data row: slot0 + k
+    int32_t carry_slot;      // the live force's data row when the launch starts (sustained0)
+    int32_t sustained0;      // the object is in sustained contact when the launch starts
+    int32_t row0, n_dense;   // its dense rows: row0 .. row0 + n_dense - 1 of the launch's stroke rows
+    int32_t proj0;           // its first ProjectEvent among the launch's stroke events
+    int32_t stream;          // its ArStream (row-parallel K2), or -1
+    int32_t ar_state;        // ArState slot of the live force
+    int32_t flags0;          // ProfEntry::flags of its first dense row (1 construct, 2 SetParam)
+    double arprm[4];         // SetParam values (flags0 & 2)
+};
+struct StrokeTables {
+    const StrokeRec *recs;
+    const int64_t *stamps;   // the script as given: [n]
+    const int32_t *vids;     // [n][3]
+    const double *coords, *vn;       // [n][3]
+    const unsigned char *flags;      // [n] or nullptr (all 0)
+    int64_t buffers_done;    // stamp of the launch's first buffer
+    int32_t nb;
+    uint32_t tile_mask;      // of a dense row
+    // device copies of the plan's tables and the number of host-planned items in front of the stroke items
+    BufDesc *desc;           // [n_obj][nb]
+    int32_t *row_ptr, *slot_idx, *row_obj, *prow_obj;
+    ProfRow *prof_rows;
+    ProfEntry *prof_entries;
+    ArUse *ar_uses;          // nullptr: K2's chain form, no AR tables
+    ProjectEvent *proj;
+    double *slots;           // data-slot pool (rows of STROKE_ZERO entries are cleared here)
+    int32_t frow_base, prow_base, sidx_base, entry_base, prof_row_base, use_base, proj_base;
+    int32_t m_pad;
+};
+int launch_stroke_expand(const StrokeTables &t, int n_recs, hipStream_t stream);
+
 struct FfatGeom {        // FFAT_Map<double,3> runtime fields, one per (object, mode)
     double k;
     double center3[3];

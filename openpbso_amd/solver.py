@@ -354,6 +354,37 @@ class Engine:
         self._borrowed = prepared[5]
         return rc
 
+    @staticmethod
+    def prepare_strokes(objs, vids, coords, vns, not_before, flags=None, force_type=capi.AUTOREGRESSIVE_FORCE):
+        """the arguments of pbso_enqueue_strokes converted once: objs / not_before [n], vids / coords / vns [n][3], flags [n] of
+        capi.STROKE_START | STROKE_END | STROKE_ZERO (None: all 0); hand the result to enqueue_prepared_strokes"""
+        o = np.ascontiguousarray(objs, dtype=np.int32)
+        v = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1, 3)
+        c = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 3)
+        n = np.ascontiguousarray(vns, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(not_before, dtype=np.int64)
+        f = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        assert o.size == t.size == v.shape[0] == c.shape[0] == n.shape[0] and (f is None or f.size == o.size)
+        return (o.size, o.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_int)), _dp(c), _dp(n),
+                t.ctypes.data_as(C.POINTER(C.c_int64)), None if f is None else f.ctypes.data_as(C.POINTER(C.c_ubyte)), int(force_type),
+                (o, v, c, n, t, f))
+
+    def enqueue_prepared_strokes(self, prepared):
+        rc = self._chk(self._l.pbso_enqueue_strokes(self._h, *prepared[:8]))
+        self._borrowed = prepared[8]                    # (only a script the engine TOOK: the arrays stay alive until the step)
+        return rc
+
+    def enqueue_strokes(self, objs, vids, coords, vns, not_before, flags=None, force_type=capi.AUTOREGRESSIVE_FORCE):
+        """pbso_enqueue_strokes: a step's contact-stroke entries as parallel arrays, object by object (ids ascending, stamps
+        ascending within an object); borrowed by the engine until the next step() returns (kept alive here)"""
+        return self.enqueue_prepared_strokes(self.prepare_strokes(objs, vids, coords, vns, not_before, flags, force_type))
+
+    def stroke_stats(self):
+        """pbso_stroke_stats: totals of stroke entries by the way they took, and launches that ran the stroke kernel"""
+        out = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_stroke_stats(self._h, out))
+        return dict(direct=out[0], queued=out[1], dropped=out[2], kernel_launches=out[3])
+
     def enqueue_arprm(self, obj, a, sigma, mu, not_before=0):
         a = np.ascontiguousarray(a, dtype=np.float64)
         return bool(self._chk(self._l.pbso_enqueue_arprm(self._h, obj, _dp(a), sigma, mu, not_before)))

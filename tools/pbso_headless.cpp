@@ -11,6 +11,11 @@
 //                    or:    <buffer> <vertex_id> - [point|gauss <width_us>|ar]   (normal = VN.row(vid) of the mesh:
 //                    igl::per_vertex_normals of the .obj, tools/...:509,607 -- needs -m / -d)
 //   --listener FILE  lines: <buffer> <x> <y> <z>          (computeTransfer at that buffer)
+//   --strokes FILE   sustained contact (the mouse dragged over the surface, tools/...:754-776, 1127-1160), lines:
+//                    <buffer> <v0> <v1> <v2> <c0> <c1> <c2> <nx> <ny> <nz> [start|end]   a GetModalForceFace message (vn as given)
+//                    <buffer> - [start|end]                                              the dummy start / stop message (setZero(N))
+//                    fed one step ahead through pbso_enqueue_strokes (with --devices: to the engines of the ranks);
+//                    --stroke-force point|ar (default ar);  --arprm "<a0> <a1> <sigma> <mu>"  AR parameters from buffer 0 on
 //   --buffers N      number of 513-sample buffers (default 86 ~ 1 s)
 //   --out FILE       output WAV (default out.wav);  --raw FILE also dumps the fp32 sound values
 //   --devices 0,1,.. several GPUs through the C ABI's device group (one engine per GPU, objects sharded by the sum of their
@@ -74,6 +79,38 @@ static void write_wav_f32(const std::string &path, const std::vector<float> &mon
 
 struct Hit { long b; pbso_force_msg m; };
 struct Pos { long b; double p[3]; };
+// --strokes: one entry of the script, and the arrays one pbso_enqueue_strokes call borrows until its step returns
+struct Stroke { long b; unsigned char flags; int v[3]; double c[3], n[3]; };
+struct StrokeFeed {
+    std::vector<int> objs, vids;
+    std::vector<double> coords, vn;
+    std::vector<int64_t> stamps;
+    std::vector<unsigned char> flags;
+};
+struct StrokeScript {
+    std::vector<Stroke> entries;                 // ascending buffers
+    int force_type = PBSO_AUTOREGRESSIVE_FORCE;
+    bool have_arprm = false;
+    double arprm[4] = {0, 0, 0, 0};
+};
+// the entries of buffers [b0, b1) for the objects `ids` (ascending) of engine e, object ids[k] hearing the script shift[k] buffers later
+static void feed_strokes(pbso_engine *e, const StrokeScript &sc, const std::vector<int> &ids, const std::vector<long> &shift, long b0, long b1,
+                         StrokeFeed &f) {
+    f = StrokeFeed();
+    for (size_t k = 0; k < ids.size(); ++k)
+        for (const Stroke &s : sc.entries) {
+            const long b = s.b + shift[k];
+            if (b < b0 || b >= b1) continue;
+            f.objs.push_back(ids[k]);
+            f.stamps.push_back(b);
+            f.flags.push_back(s.flags);
+            for (int j = 0; j < 3; ++j) { f.vids.push_back(s.v[j]); f.coords.push_back(s.c[j]); f.vn.push_back(s.n[j]); }
+        }
+    if (f.objs.empty()) return;
+    const int rc = pbso_enqueue_strokes(e, (int)f.objs.size(), f.objs.data(), f.vids.data(), f.coords.data(), f.vn.data(), f.stamps.data(),
+                                        f.flags.data(), sc.force_type);
+    check(e, rc, "enqueue_strokes");
+}
 // --channels / --pan: the scene mix's script
 struct Pan { long b; int copy; std::vector<float> gd; };   // gd: g_0 d_0 ... g_{C-1} d_{C-1}
 struct Scene {
@@ -104,8 +141,8 @@ struct Scene {
 
 // the scene on several GPUs (include/openpbso_amd.h "device group")
 static int run_group(const std::vector<int> &devices, int copies, int shift, const std::string &modes, const std::string &material,
-                     const std::string &ffat, const std::vector<Hit> &hits, const std::vector<Pos> &path, int n_buffers,
-                     const Scene *scene, std::vector<float> &sound) {
+                     const std::string &ffat, const std::vector<Hit> &hits, const std::vector<Pos> &path, const StrokeScript &strokes,
+                     int n_buffers, const Scene *scene, std::vector<float> &sound) {
     auto gcheck = [](pbso_group *g, int rc, const char *what) {
         if (rc < 0) die(std::string(what) + ": " + pbso_status_string(rc) + ": " + (g ? pbso_group_last_error(g) : ""));
     };
@@ -158,7 +195,23 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             gcheck(g, rc, "group_enqueue_force");
             if (rc == 0) die("force queue full");
         }
+        if (strokes.have_arprm) check(e, pbso_enqueue_arprm(e, local, strokes.arprm, strokes.arprm[2], strokes.arprm[3], (long)c * shift), "enqueue_arprm");
     }
+    // the stroke script goes to the engines of the ranks, every rank its own copies (ascending local ids), step by step
+    std::vector<std::vector<int>> rank_ids(devices.size());
+    std::vector<std::vector<long>> rank_shift(devices.size());
+    for (int c = 0; c < copies && !strokes.entries.empty(); ++c) {
+        int rank = 0, local = 0;
+        gcheck(g, pbso_group_owner(g, c, &rank, &local), "group_owner");
+        auto at = std::lower_bound(rank_ids[rank].begin(), rank_ids[rank].end(), local) - rank_ids[rank].begin();
+        rank_ids[rank].insert(rank_ids[rank].begin() + at, local);
+        rank_shift[rank].insert(rank_shift[rank].begin() + at, (long)c * shift);
+    }
+    std::vector<StrokeFeed> feeds(devices.size());
+    auto feed_ranks = [&](long b0, long b1) {
+        for (size_t r = 0; r < devices.size(); ++r)
+            if (!rank_ids[r].empty()) feed_strokes(pbso_group_engine(g, (int)r), strokes, rank_ids[r], rank_shift[r], b0, b1, feeds[r]);
+    };
     if (scene) {
         // the segments between the pan script's change points, each gathered as a C-channel scene mix: sound [C][n_buffers * B]
         const int C = scene->channels;
@@ -171,6 +224,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
             const int nb = cuts[k + 1] - cuts[k];
             const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
+            feed_ranks(cuts[k], cuts[k + 1]);
             gcheck(g, pbso_group_step(g, nb), "group_step");
             gcheck(g, pbso_group_gather(g, PBSO_GATHER_SCENE), "group_gather");
             seg.resize((size_t)C * row);
@@ -180,6 +234,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
                           sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
         }
     } else {
+        feed_ranks(0, n_buffers);
         gcheck(g, pbso_group_step(g, n_buffers), "group_step");
         gcheck(g, pbso_group_gather(g, PBSO_GATHER_MIX), "group_gather");
         sound.resize((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
@@ -197,7 +252,8 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, listener, out = "out.wav", raw, devices_arg, pan;
+    std::string d, name, mesh, modes, material, ffat, hits, listener, out = "out.wav", raw, devices_arg, pan, strokes_file, arprm_arg;
+    StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
     for (int i = 1; i < argc; ++i) {
@@ -211,6 +267,14 @@ int main(int argc, char **argv) {
         else if (a == "-p" || a == "--ffat_map") ffat = val();
         else if (a == "--hits") hits = val();
         else if (a == "--listener") listener = val();
+        else if (a == "--strokes") strokes_file = val();
+        else if (a == "--stroke-force") {
+            const std::string t = val();
+            if (t == "point") strokes.force_type = PBSO_POINT_FORCE;
+            else if (t == "ar") strokes.force_type = PBSO_AUTOREGRESSIVE_FORCE;
+            else die("--stroke-force must be point or ar");
+        }
+        else if (a == "--arprm") arprm_arg = val();
         else if (a == "--buffers") n_buffers = std::atoi(val().c_str());
         else if (a == "--out") out = val();
         else if (a == "--raw") raw = val();
@@ -306,6 +370,40 @@ int main(int argc, char **argv) {
         }
     }
 
+    if (!strokes_file.empty()) {
+        std::ifstream f(strokes_file);
+        if (!f) die("cannot read " + strokes_file);
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            Stroke s;
+            std::memset(&s, 0, sizeof(s));
+            std::string tok, flag;
+            if (!(iss >> s.b >> tok)) die("bad stroke line: " + line);
+            if (tok == "-") {
+                s.flags = PBSO_STROKE_ZERO;
+            } else {
+                s.v[0] = std::atoi(tok.c_str());
+                if (!(iss >> s.v[1] >> s.v[2] >> s.c[0] >> s.c[1] >> s.c[2] >> s.n[0] >> s.n[1] >> s.n[2])) die("bad stroke line: " + line);
+                for (int j = 0; j < 3; ++j)
+                    if (s.v[j] < 0 || 3 * s.v[j] + 2 >= n_dof) die("vertex id out of range: " + line);
+            }
+            if (iss >> flag) {
+                if (flag == "start") s.flags |= PBSO_STROKE_START;
+                else if (flag == "end") s.flags |= PBSO_STROKE_END;
+                else die("bad stroke line (start or end): " + line);
+            }
+            if (s.b < 0) die("bad stroke line: " + line);
+            strokes.entries.push_back(s);
+        }
+        std::stable_sort(strokes.entries.begin(), strokes.entries.end(), [](const Stroke &a, const Stroke &b) { return a.b < b.b; });
+    }
+    if (!arprm_arg.empty()) {
+        std::istringstream iss(arprm_arg);
+        if (!(iss >> strokes.arprm[0] >> strokes.arprm[1] >> strokes.arprm[2] >> strokes.arprm[3])) die("--arprm needs \"<a0> <a1> <sigma> <mu>\"");
+        strokes.have_arprm = true;
+    }
     std::vector<int> devices;
     if (!devices_arg.empty()) {
         std::istringstream ds(devices_arg);
@@ -345,7 +443,7 @@ int main(int argc, char **argv) {
     std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
     double device_ms = 0;
     if (!devices.empty()) {
-        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, path, n_buffers, mixed ? &scene : nullptr, sound);
+        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, path, strokes, n_buffers, mixed ? &scene : nullptr, sound);
     } else {
         pbso_engine_desc desc;
         std::memset(&desc, 0, sizeof(desc));
@@ -366,6 +464,10 @@ int main(int argc, char **argv) {
             check(e, rc, "enqueue_force");
             if (rc == 0) die("force queue full");
         }
+        if (strokes.have_arprm) check(e, pbso_enqueue_arprm(e, obj, strokes.arprm, strokes.arprm[2], strokes.arprm[3], 0), "enqueue_arprm");
+        StrokeFeed feed;                                     // (borrowed by the engine until the step that follows returns)
+        const std::vector<int> stroke_ids{obj};
+        const std::vector<long> stroke_shift{0};
         if (mixed) {
             // the one object through the scene mixer, segment by segment: sound [C][n_buffers * B]
             const int C = scene.channels;
@@ -378,6 +480,7 @@ int main(int argc, char **argv) {
                 if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
                 const int nb = cuts[k + 1] - cuts[k];
                 const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
+                feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], cuts[k + 1], feed);
                 check(e, pbso_step(e, nb), "step");
                 check(e, pbso_scene_mix(e, nullptr), "scene_mix");
                 seg.resize((size_t)C * row);
@@ -387,6 +490,7 @@ int main(int argc, char **argv) {
                               sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
             }
         } else {
+            feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
             check(e, pbso_step(e, n_buffers), "step");
             check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
         }
