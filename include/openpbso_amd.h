@@ -55,7 +55,8 @@ enum pbso_status {
 enum pbso_force_type {
     PBSO_POINT_FORCE = 0,
     PBSO_GAUSSIAN_FORCE = 1,
-    PBSO_AUTOREGRESSIVE_FORCE = 2
+    PBSO_AUTOREGRESSIVE_FORCE = 2,
+    PBSO_TRACK_FORCE = 3      /* not in the reference: plays a caller-supplied signal, see pbso_enqueue_track_force */
 };
 
 /* how the spatial (modal) part of a force message is given */
@@ -320,6 +321,50 @@ int pbso_enqueue_strokes(pbso_engine *e, int n, const int *object_ids, const int
 /* totals since the engine was created: out[0] stroke entries taken straight into descriptors, out[1] entries that went through
  * the queue, out[2] entries dropped (full queue), out[3] launches that ran the stroke kernel */
 int pbso_stroke_stats(pbso_engine *e, int64_t out[4]);
+/* --- force tracks: contacts driven by caller-supplied force signals ----------------------------------------------------------
+ * A TRACK is an immutable mono f32 signal in device memory, owned by the engine.  A TRACK FORCE is a fourth Force subclass in
+ * the sense of forces.h:18-23: a message of type PBSO_TRACK_FORCE carries a PLAY RECORD saying which part of which track it
+ * plays, at what rate and gain, and at which sample of its first buffer it starts.  Everything else about the message -- its
+ * spatial vector, the sustained flags, clear_all_forces, the 1023-slot queue, not_before -- is what it is for the other three
+ * types, and ModalSolver::step's bookkeeping (modal_solver.h:184-240) applies unchanged, including that a buffer's force is
+ * (sum of data) x (sum of profiles).
+ * Semantics (fp64, no fused multiply-add, this order).  s[0 .. L-1] the track; S(j) = s[j] for 0 <= j < L and 0 otherwise, or
+ * with loop s[j mod L].  For p >= 0, i = floor(p), f = p - i:  x(p) = S(i) + f * (S(i + 1) - S(i)).  Output sample k = 0, 1, ... of
+ * the force is gain * x(first + rate * (double)k) -- from the 64-bit index k, never an accumulated position, so a row does not
+ * depend on how a run is cut into steps.  The force lasts N output samples: n_samples if > 0 (positions past the track read
+ * zeros); else without loop the number of k with first + rate * k < L; with loop for ever.  Add(buf), once per buffer from the
+ * buffer that dequeued the message on: exhausted (k0 >= N) -> false; else buf[i] += v_k for i = o .. frames - 1 while k < N, with
+ * o = start_sample in the first buffer and 0 afterwards.  Like a GaussianForce it returns true in the buffer that holds its
+ * last sample and is erased by the Add of the buffer after; under sustained contact an exhausted track adds nothing and stays.
+ * A one-sample track is a hit at sample start_sample of its buffer: the reference admits a force at sample 0 only.
+ * Out of scope: track forces in pbso_enqueue_strokes (a sustained track scene is planned per (object, buffer) on the host like
+ * any message feed); a cheap descriptor for "one sample at offset s" (such a hit is a dense profile row and runs the
+ * dense-profile path, slower than the impulse path); independent signals at several contact points of ONE object in one
+ * buffer (they multiply as (sum data)(sum profiles), the reference's step(): add the object twice and mix, the bank is
+ * linear); interpolation better than linear, tracks in fp64, freeing a track. */
+typedef struct pbso_track_play {
+    int track;            /* id from pbso_track_create */
+    int loop;             /* != 0: read positions wrap around the track's length */
+    int start_sample;     /* in-buffer index of output sample 0, in the buffer that dequeues the message: 0 .. frames - 1 */
+    int reserved;         /* 0 */
+    int64_t n_samples;    /* output samples the force lasts; 0 = until the read position leaves the track (with loop: for ever) */
+    double first;         /* read position of output sample 0, in track samples; >= 0, may be fractional */
+    double rate;          /* track samples per output sample; finite, > 0 */
+    double gain;          /* finite */
+} pbso_track_play;
+/* Copies n >= 1 finite samples into the engine's track pool before it returns; ids count from 0; tracks live until the engine
+ * is destroyed.  Any time after pbso_engine_create, before or after pbso_finalize.  NOT a hot-loop call: when the pool has to
+ * grow while launches are in flight, the call waits for them (and for the submitting thread).  PBSO_ERR_INVALID: n < 1, a
+ * sample that is not finite. */
+int pbso_track_create(pbso_engine *e, const float *samples, int64_t n, int *track_id);
+/* pbso_enqueue_force for a message with m->force_type == PBSO_TRACK_FORCE and its play record, validated here
+ * (PBSO_ERR_INVALID, pbso_last_error names the field).  1 = enqueued, 0 = the queue is full.  pbso_enqueue_force / _batch
+ * reject PBSO_TRACK_FORCE: a track force without a play record means nothing. */
+int pbso_enqueue_track_force(pbso_engine *e, int object_id, const pbso_force_msg *m, const pbso_track_play *play,
+                             int64_t not_before);
+/* totals since the engine was created: out[0] tracks created, out[1] samples held, out[2] track-force messages dequeued by
+ * step, out[3] profile rows that contained at least one track entry */
+int pbso_track_stats(pbso_engine *e, int64_t out[4]);
 /* ModalSolver::enqueueArprmMessageNoFail (modal_solver.h:382-393); 1-slot queue: a message that finds the slot taken waits in
  * the engine and enters when step() has taken the one before it (the reference's caller spins on try_enqueue meanwhile) */
 int pbso_enqueue_arprm(pbso_engine *e, int object_id, const double a[2], double sigma,

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PBSO_LIB") or os.path.join(_HERE, "libopenpbso_amd.so
 ABI_VERSION = 6
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_IO, ERR_MISSING_MAP, ERR_ASSERT, ERR_NOMEM = -1, -2, -3, -4, -5, -6, -7
-POINT_FORCE, GAUSSIAN_FORCE, AUTOREGRESSIVE_FORCE = 0, 1, 2
+POINT_FORCE, GAUSSIAN_FORCE, AUTOREGRESSIVE_FORCE, TRACK_FORCE = 0, 1, 2, 3
 DATA_EXPLICIT, DATA_VERTEX, DATA_FACE, DATA_ZERO = 0, 1, 2, 3
 FORM_BLOCK, FORM_VELOCITY, FORM_DIRECT, FORM_BLOCK_BF16 = 0, 1, 2, 3
 QNORM_OFF, QNORM_ALL, QNORM_CLOSED = 0, 1, 2
@@ -35,6 +35,8 @@ EXPORTS = [
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
     "pbso_group_enqueue_force", "pbso_group_step", "pbso_group_gather", "pbso_group_sync", "pbso_group_result_device_ptr",
     "pbso_group_read_result", "pbso_shard_by_modes", "pbso_group_scene_mix_enable", "pbso_group_scene_mix_set",
+    # force tracks (caller-supplied force signals played by PBSO_TRACK_FORCE messages)
+    "pbso_track_create", "pbso_enqueue_track_force", "pbso_track_stats",
 ]
 STROKE_START, STROKE_END, STROKE_ZERO = 1, 2, 4      # pbso_enqueue_strokes flags
 GATHER_ALL, GATHER_ROOT, GATHER_MIX, GATHER_SCENE = 1, 2, 3, 4
@@ -79,6 +81,12 @@ class ForceMsg(C.Structure):
                 ("clear_all_forces", C.c_int), ("data_kind", C.c_int),
                 ("data", C.POINTER(C.c_double)), ("n_data", C.c_int), ("vids", C.c_int * 3),
                 ("coords", C.c_double * 3), ("vn", C.c_double * 3)]
+
+
+class TrackPlay(C.Structure):
+    """pbso_track_play: which part of which track a PBSO_TRACK_FORCE message plays"""
+    _fields_ = [("track", C.c_int), ("loop", C.c_int), ("start_sample", C.c_int), ("reserved", C.c_int),
+                ("n_samples", C.c_int64), ("first", C.c_double), ("rate", C.c_double), ("gain", C.c_double)]
 
 
 class EngineInfo(C.Structure):
@@ -137,6 +145,11 @@ def lib():
     l.pbso_enqueue_strokes.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.c_int]
     l.pbso_stroke_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_track_create"):
+        # (an older build picked with PBSO_LIB for an A/B run has no tracks: using them fails there, where the call is made)
+        l.pbso_track_create.argtypes = [vp, C.POINTER(C.c_float), C.c_int64, ip]
+        l.pbso_enqueue_track_force.argtypes = [vp, C.c_int, C.POINTER(ForceMsg), C.POINTER(TrackPlay), C.c_int64]
+        l.pbso_track_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     l.pbso_enqueue_force_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(ForceMsg), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_ubyte)]
     l.pbso_enqueue_arprm.argtypes = [vp, C.c_int, dp, C.c_double, C.c_double, C.c_int64]

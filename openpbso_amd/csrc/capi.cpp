@@ -307,6 +307,30 @@ int pbso_stroke_stats(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_track_create(pbso_engine *e, const float *samples, int64_t n, int *track_id) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->track_create(samples, n, track_id);
+    GUARD_END(e)
+}
+
+int pbso_enqueue_track_force(pbso_engine *e, int obj, const pbso_force_msg *m, const pbso_track_play *play, int64_t nb) {
+    NEED(e);
+    if (!m || !play) return PBSO_ERR_INVALID;
+    GUARD_BEGIN
+    return e->impl->enqueue_track_force(obj, *m, *play, nb);
+    GUARD_END(e)
+}
+
+int pbso_track_stats(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    if (!out) return PBSO_ERR_INVALID;
+    GUARD_BEGIN
+    e->impl->track_stats(out);
+    return PBSO_OK;
+    GUARD_END(e)
+}
+
 int pbso_enqueue_arprm(pbso_engine *e, int obj, const double a[2], double sigma, double mu, int64_t nb) {
     NEED(e);
     if (!a) return PBSO_ERR_INVALID;

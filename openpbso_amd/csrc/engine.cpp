@@ -156,7 +156,53 @@ ForceProfile ForceProfile::make(int type, double gaussian_width_us, int sample_r
     return f;
 }
 
-bool ForceProfile::add(double *t, int frames, int *extent) {
+// the tiles that samples [first, first + n) of a buffer intersect, n > 0 (BufDesc::tile_mask)
+static inline uint32_t tiles_of(int first, int n) {
+    const int lo = first / TILE, hi = (first + n - 1) / TILE;
+    return (hi >= 31 ? 0xFFFFFFFFu : ((1u << (hi + 1)) - 1u)) & ~((1u << lo) - 1u);
+}
+
+// TrackForce::Add's bookkeeping (include/openpbso_amd.h): `for i = o .. frames - 1, k = k0 + (i - o), while k < N`
+bool ForceProfile::track_span(int frames, int *first_index, int *n_live, int64_t *k0) {
+    Track &t = *track;
+    if (t.k0 >= t.total) return false;
+    const int o = t.offset;
+    *first_index = o;
+    *k0 = t.k0;
+    *n_live = (int)std::min<int64_t>(frames - o, t.total - t.k0);
+    t.k0 += frames - o;
+    t.offset = 0;
+    return true;
+}
+
+// x(p) of a track (include/openpbso_amd.h): the arithmetic of track_add in kernels_exact.hip, in its order (no FMA: see track_sample_at's
+// callers -- the expression is written so that the compiler has nothing to contract)
+static double track_value(const float *s, int64_t L, bool loop, double first, double rate, double gain, int64_t k) {
+    volatile double prod = rate * (double)k;               // (volatile: the product and the sum round separately on every host compiler)
+    const double p = first + prod;
+    double x = 0.0;
+    if (p >= 0.0 && p < 9.0e18) {
+        const double fl = std::floor(p);
+        const double f = p - fl;
+        int64_t i0 = (int64_t)fl, i1;
+        double s0 = 0.0, s1 = 0.0;
+        if (loop) {
+            i0 %= L;
+            i1 = i0 + 1 == L ? 0 : i0 + 1;
+            s0 = (double)s[i0];
+            s1 = (double)s[i1];
+        } else {
+            i1 = i0 + 1;
+            if (i0 < L) s0 = (double)s[i0];
+            if (i1 < L) s1 = (double)s[i1];
+        }
+        volatile double d = f * (s1 - s0);
+        x = s0 + d;
+    }
+    return gain * x;
+}
+
+bool ForceProfile::add(double *t, int frames, int *extent, uint32_t *live_tiles) {
     switch (type) {
     case PBSO_POINT_FORCE:                                   // forces.h:81-90
         if (used) return false;
@@ -184,6 +230,16 @@ bool ForceProfile::add(double *t, int frames, int *extent) {
             t[ii] += mu + mu_tilde;
         }
         return true;
+    case PBSO_TRACK_FORCE: {
+        int o, n_live;
+        int64_t k0;
+        if (!track_span(frames, &o, &n_live, &k0)) return false;
+        *extent = std::max(*extent, o + n_live);
+        for (int j = 0; j < n_live; ++j)
+            t[o + j] += track_value(track->samples, track->len, track->play.loop != 0, track->play.first, track->play.rate, track->play.gain, k0 + j);
+        if (live_tiles && n_live > 0) *live_tiles |= tiles_of(o, n_live);
+        return true;
+    }
     }
     return false;
 }
@@ -228,6 +284,7 @@ Engine::~Engine() {
         std::fprintf(stderr, "pbso stroke kernel: %.4f ms per launch over %lld launches (HIP events)\n", stroke_kernel_ms_ / stroke_kernel_n_,
                      (long long)stroke_kernel_n_);
     free_retired_blocks();
+    track_release();
     d_ca_.release(); d_cb_.release(); d_sq_.release(); d_sd_.release(); d_ss_.release(); d_c3_.release(); d_gq_.release();
     d_shapes_.release(); d_shape_off_.release(); d_g32_.release(); d_g32_off_.release(); d_n_modes_.release(); d_geom_.release();
     d_geom_off_.release(); d_psi_.release(); d_psi_t_.release(); d_ffat_k_.release(); d_ffat_valid_.release(); d_ffat_shared_.release(); d_slots_.release(); d_xfer_.release();
@@ -1177,12 +1234,14 @@ int Engine::warm_copy_engines() {
 
 // ---------------------------------------------------------------------------
 // ModalSolver::enqueueForceMessage, modal_solver.h:329-333
-int Engine::enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why) {
+int Engine::enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why, const pbso_track_play *play,
+                               int64_t track_total) {
     if (!finalized_) { *why = "enqueue_force before finalize"; return PBSO_ERR_STATE; }
     if (!valid_obj(obj)) { *why = "object id"; return PBSO_ERR_INVALID; }
     Object &o = objs_[obj];
-    if (m.force_type < PBSO_POINT_FORCE || m.force_type > PBSO_AUTOREGRESSIVE_FORCE)
-        { *why = "unrecognized force type"; return PBSO_ERR_INVALID; }             // assert modal_solver.h:73
+    if (m.force_type < PBSO_POINT_FORCE || m.force_type > (play ? PBSO_TRACK_FORCE : PBSO_AUTOREGRESSIVE_FORCE))
+        { *why = m.force_type == PBSO_TRACK_FORCE ? "a track force needs a play record: pbso_enqueue_track_force" : "unrecognized force type";
+          return PBSO_ERR_INVALID; }                                               // assert modal_solver.h:73
     HostForceMsg h;
     h.force_type = m.force_type;
     h.sustained_start = m.sustained_force_start != 0;
@@ -1191,13 +1250,14 @@ int Engine::enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_bef
     h.data_kind = m.data_kind;
     h.not_before = not_before;
     // (the Force object itself is built when the message is dequeued)
-    const bool need_ext = m.data_kind == PBSO_DATA_FACE || m.gaussian_width_us != 0.0 ||
+    const bool need_ext = play || m.data_kind == PBSO_DATA_FACE || m.gaussian_width_us != 0.0 ||
                           (m.data_kind == PBSO_DATA_EXPLICIT && !h.clear_all);
     auto make_ext = [&](int n_data) {
-        MsgExt *x = (MsgExt *)std::malloc(sizeof(MsgExt) + sizeof(double) * (size_t)(n_data > 0 ? n_data - 1 : 0));
+        MsgExt *x = (MsgExt *)std::malloc(sizeof(MsgExt) + sizeof(double) * (size_t)(n_data > 0 ? n_data - 1 : 0) + (play ? sizeof(TrackExt) : 0));
         x->coords[0] = m.coords[0]; x->coords[1] = m.coords[1]; x->coords[2] = m.coords[2];
         x->gaussian_width_us = m.gaussian_width_us;
         x->n_data = n_data;
+        if (play) { track_ext(x)->play = *play; track_ext(x)->total = track_total; }
         return x;
     };
     switch (m.data_kind) {
@@ -1535,6 +1595,38 @@ int Engine::enqueue_force(int obj, const pbso_force_msg &m, int64_t not_before) 
     return rc < 0 ? fail(rc, why) : rc;
 }
 
+// pbso_enqueue_track_force: the message of pbso_enqueue_force with force_type PBSO_TRACK_FORCE and its play record, validated here.
+// The number of output samples the play lasts is fixed here too, with the fp64 expression the kernel and the host profile use.
+int Engine::enqueue_track_force(int obj, const pbso_force_msg &m, const pbso_track_play &play, int64_t not_before) {
+    if (!finalized_) return fail(PBSO_ERR_STATE, "enqueue_track_force before finalize");
+    if (m.force_type != PBSO_TRACK_FORCE) return fail(PBSO_ERR_INVALID, "enqueue_track_force: force_type must be PBSO_TRACK_FORCE");
+    const int64_t L = track_length(play.track);
+    if (L < 0) return fail(PBSO_ERR_INVALID, "pbso_track_play: track is not an id pbso_track_create returned");
+    if (play.start_sample < 0 || play.start_sample >= B_) return fail(PBSO_ERR_INVALID, "pbso_track_play: start_sample must be 0 .. frames - 1");
+    if (play.reserved != 0) return fail(PBSO_ERR_INVALID, "pbso_track_play: reserved must be 0");
+    if (play.n_samples < 0) return fail(PBSO_ERR_INVALID, "pbso_track_play: n_samples must be >= 0");
+    if (!std::isfinite(play.first) || play.first < 0.0) return fail(PBSO_ERR_INVALID, "pbso_track_play: first must be finite and >= 0");
+    if (!std::isfinite(play.rate) || !(play.rate > 0.0)) return fail(PBSO_ERR_INVALID, "pbso_track_play: rate must be finite and > 0");
+    if (!std::isfinite(play.gain)) return fail(PBSO_ERR_INVALID, "pbso_track_play: gain must be finite");
+    int64_t N;
+    if (play.n_samples > 0) N = play.n_samples;
+    else if (play.loop) N = INT64_MAX;
+    else if (play.first >= (double)L) N = 0;
+    else {
+        // the number of k with first + rate * k < L: an estimate, then a step up or down with that very expression
+        auto pos = [&](int64_t k) { volatile double prod = play.rate * (double)k; return play.first + prod; };
+        const double est = ((double)L - play.first) / play.rate;
+        N = est < 9.0e18 ? (int64_t)est : (int64_t)9.0e18;
+        if (N < 1) N = 1;
+        while (N > 0 && !(pos(N - 1) < (double)L)) --N;
+        while (N < INT64_MAX - 1 && pos(N) < (double)L) ++N;
+    }
+    if (script_.n > 0) { int frc = flush_script(); if (frc != PBSO_OK) return frc; }
+    const char *why = "";
+    const int rc = enqueue_force_impl(obj, m, not_before, &why, &play, N);
+    return rc < 0 ? fail(rc, why) : rc;
+}
+
 // A whole step of a force script.  Messages of one object keep their order.  With planner threads
 // (PBSO_PLAN_THREADS > 1) every thread enqueues the messages of its own range of objects.
 int Engine::enqueue_force_batch(int n, const int *objs, const pbso_force_msg *msgs, const int64_t *stamps,
@@ -1869,6 +1961,13 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
         af.slot = slot;
         af.force_type = mess.force_type;
         af.force = ForceProfile::make(mess.force_type, mess.gaussian_width_us(), rate_);   // fresh Force, tools/...:281-294
+        if (mess.force_type == PBSO_TRACK_FORCE) {
+            const TrackExt &te = *track_ext(mess.ext);
+            af.force.track = std::make_shared<ForceProfile::Track>(ForceProfile::Track{
+                te.play, te.total, 0, te.play.start_sample, device_profiles_ ? nullptr : track_host_samples(te.play.track),
+                track_length(te.play.track)});
+            track_msgs_.fetch_add(1, std::memory_order_relaxed);
+        }
         bool slot_used = false;
         if (mess.sustained_start) {                                     // :190-194
             for (ActiveForce &x : o.active) release(c, x);
@@ -1906,7 +2005,8 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
         const int row_begin = (int)c.slot_idx.size();
         const int entry_begin = (int)c.prof_entries.size();
         int n_point = 0;
-        bool dense = false;
+        bool dense = false, dense_all_tiles = false;
+        uint32_t track_tiles = 0;
         auto emit = [&](ActiveForce &af, bool set_param) -> bool {
             ForceProfile &f = af.force;
             ProfEntry e;
@@ -1925,8 +2025,23 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
                 e.center = f.center;
                 e.width_samples = f.width_samples;
                 f.count += B_;
-                dense = true;
+                dense = dense_all_tiles = true;
                 break;
+            case PBSO_TRACK_FORCE: {                                 // include/openpbso_amd.h, pbso_track_play; ProfEntry's track layout
+                int o_first, n_live;
+                int64_t k0;
+                if (!f.track_span(B_, &o_first, &n_live, &k0)) return false;
+                e.state = f.track->play.track;
+                e.flags = f.track->play.loop ? 1 : 0;
+                e.count = o_first;
+                e.center = n_live;
+                e.a0 = f.track->play.first; e.a1 = f.track->play.rate; e.sigma = f.track->play.gain;
+                e.mu = track_k0_bits(k0);
+                if (n_live > 0) track_tiles |= tiles_of(o_first, n_live);
+                dense = true;
+                c.prof_entries.push_back(e);
+                return true;
+            }
             default:                                                 // forces.h:107-137
                 if (af.ar_state < 0) {
                     if (!c.free_ar.empty()) { af.ar_state = c.free_ar.back(); c.free_ar.pop_back(); }
@@ -1938,7 +2053,7 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
                     e.a0 = o.arprm[0]; e.a1 = o.arprm[1]; e.sigma = o.arprm[2]; e.mu = o.arprm[3];
                 }
                 e.state = af.ar_state;
-                dense = true;
+                dense = dense_all_tiles = true;
                 break;
             }
             c.prof_entries.push_back(e);
@@ -1989,7 +2104,9 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
             } else {
                 d.prow = c.n_prows++;
                 c.prow_obj.push_back(oi);
-                d.tile_mask = n_tiles_ >= 32 ? 0xFFFFFFFFu : ((1u << n_tiles_) - 1u);
+                // (a row of track entries only: the tiles its live samples intersect, and tile 0 for a PointForce beside them)
+                d.tile_mask = dense_all_tiles ? (n_tiles_ >= 32 ? 0xFFFFFFFFu : ((1u << n_tiles_) - 1u)) : (track_tiles | (n_point ? 1u : 0u));
+                if (track_tiles) track_rows_.fetch_add(1, std::memory_order_relaxed);
                 ProfRow pr = {d.prow, entry_begin, (int)c.prof_entries.size()};
                 c.prof_rows.push_back(pr);
                 if (c.chain_obj != oi) {           // rows of one object are contiguous (object-major plan)
@@ -2005,12 +2122,15 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
         double *T = c.tbuf.data();
         std::fill(T, T + c.t_extent, 0.0);
         c.t_extent = 0;
+        c.t_live_tiles = 0;
+        bool track_added = false;
         const int row_begin = (int)c.slot_idx.size();
         if (!o.sustained) {
             size_t w = 0;
             for (size_t r = 0; r < o.active.size(); ++r) {
                 ActiveForce &af = o.active[r];
-                const bool added = af.force.add(T, B_, &c.t_extent);
+                const bool added = af.force.add(T, B_, &c.t_extent, &c.t_live_tiles);
+                track_added = track_added || (added && af.force.type == PBSO_TRACK_FORCE);
                 if (!added) {
                     release(c, af);                                            // erase
                 } else {
@@ -2028,9 +2148,10 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
                 o.arprm_full = false;
                 af.force.set_param(o.arprm, o.arprm[2], o.arprm[3]);
             }
-            af.force.add(T, B_, &c.t_extent);
+            if (af.force.add(T, B_, &c.t_extent, &c.t_live_tiles) && af.force.type == PBSO_TRACK_FORCE) track_added = true;
             c.slot_idx.push_back(af.slot);
         }
+        if (track_added) track_rows_.fetch_add(1, std::memory_order_relaxed);
         uint32_t mask = 0;
         int last_nz = -1;
         for (int i = 0; i < c.t_extent; ++i)
@@ -2038,7 +2159,7 @@ int Engine::plan_object(PlanCtx &c, int oi, int b, int nb, int64_t t) {
         if ((int)c.slot_idx.size() > row_begin && mask) {
             d.frow = c.n_frows++;
             c.forced.push_back(&d);
-            d.tile_mask = mask;
+            d.tile_mask = mask | c.t_live_tiles;               // (the mask the device-profile path gives a row of track entries)
             c.row_obj.push_back(oi);
             c.row_ptr.push_back((int)c.slot_idx.size());
             if (last_nz == 0) {
@@ -2859,18 +2980,21 @@ int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_
         QLAUNCH(launch_force_rows_combine, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse),
                                             reinterpret_cast<const ArStream *>(da + o_arstream), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p,
                                             d_ar_vnorm_.p, d_ar_vstate_.p, d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p,
-                                            ps.d_tprof.p, B_, b_pad_, b_pad_, d_row_ptr, d_slot_idx, d_row_obj, n_frows, d_slots_.p, d_c3_.p,
+                                            ps.d_tprof.p, track_device_pool(), track_device_table(), B_, b_pad_, b_pad_, d_row_ptr, d_slot_idx,
+                                            d_row_obj, n_frows, d_slots_.p, d_c3_.p,
                                             grows.p, d_projd, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, m_pad_, (int)proj_direct_.size(),
                                             d_stage, d_stage_slot, sp);
     else if (device_profiles_ && k2_rows_launch_)
         QLAUNCH(launch_force_rows, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse), n_ar_uses,
                                     reinterpret_cast<const ArStream *>(da + o_arstream), reinterpret_cast<const int *>(da + o_arseg),
                                     (int)seg_stream_.size(), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p, d_ar_vnorm_.p, d_ar_vstate_.p,
-                                    d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p, ps.d_tprof.p, B_, b_pad_, b_pad_,
+                                    d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p, ps.d_tprof.p, track_device_pool(),
+                                    track_device_table(), B_, b_pad_, b_pad_,
                                     /* every AR force adds its samples once (a launch of one buffer): one launch instead of three */
                                     fuse_short_ && n_ar_uses > 0 && (size_t)n_ar_uses == ar_streams_.size(), sp);
     else if (device_profiles_)
-        QLAUNCH(launch_force_profiles, d_chain, n_chains, d_prow, d_pent, d_arstate_.p, ps.d_tprof.p, B_, b_pad_, ar_serial_ ? 1 : 0, k2_prio_, sp);
+        QLAUNCH(launch_force_profiles, d_chain, n_chains, d_prow, d_pent, d_arstate_.p, ps.d_tprof.p, track_device_pool(), track_device_table(),
+                                        B_, b_pad_, ar_serial_ ? 1 : 0, k2_prio_, sp);
     if (evq.has_k2) QHIP(hipEventRecord, evq.f1, sp);
     if (!fuse_combine) QLAUNCH(launch_scatter_rows, d_stage, d_stage_slot, (int)stage_slot_.size(), d_slots_.p, m_pad_, sa);
     QLAUNCH(launch_modal_project, d_proj, n_proj, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, d_slots_.p, m_pad_, sa);

@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <atomic>
 #include <deque>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
@@ -23,6 +24,7 @@
 namespace pbso {
 class SubmitQueue;       // submit_queue.h
 struct SceneMix;         // scene_mix.cpp
+struct TrackPool;        // track_pool.cpp
 
 // ---- growable device / pinned-host buffers ---------------------------------
 template <class T>
@@ -53,9 +55,25 @@ struct ForceProfile {
     double a[2] = {0.783, 0.116}, sigma = 0.00148, mu = 0.142;
     std::default_random_engine generator;                // default seed, copied with the message
     std::normal_distribution<double> distribution;
+    // TrackForce (include/openpbso_amd.h, pbso_track_play): the play record, how many output samples it lasts (INT64_MAX:
+    // for ever), the output index of the next buffer's first sample, the in-buffer offset of the first buffer (0 afterwards);
+    // samples: the host copy of the track (engines with host profiles only).  Behind a pointer: every dequeued message
+    // builds a ForceProfile, and only a track force needs these 90 bytes
+    struct Track {
+        pbso_track_play play;
+        int64_t total, k0;
+        int offset;
+        const float *samples;
+        int64_t len;
+    };
+    std::shared_ptr<Track> track;
+    // TrackForce::Add's bookkeeping for one buffer: false when the play is exhausted; else the in-buffer index of its first
+    // live sample, how many samples of this buffer are live, the output index of the first one -- and the play moves on
+    bool track_span(int frames, int *first_index, int *n_live, int64_t *k0);
     static ForceProfile make(int type, double gaussian_width_us, int sample_rate);
     // Force::Add, forces.h:81-128.  *extent grows to the number of leading samples it touched.
-    bool add(double *t, int frames, int *extent);
+    // (a TrackForce also reports the tiles its live samples intersect: *live_tiles |= ...)
+    bool add(double *t, int frames, int *extent, uint32_t *live_tiles = nullptr);
     void set_param(const double a_[2], double sigma_, double mu_);   // forces.h:130-137
 };
 
@@ -69,6 +87,10 @@ struct MsgExt {
     int n_data;
     double data[1];                                      // n_data doubles (ForceMessage::data as the GUI built it)
 };
+// a PBSO_TRACK_FORCE message carries its play record and the number of output samples it lasts BEHIND data[n_data] of its
+// block (the blocks of the other messages -- a scene's worth per step -- stay as small as they were)
+struct TrackExt { pbso_track_play play; int64_t total; };
+inline TrackExt *track_ext(MsgExt *x) { return reinterpret_cast<TrackExt *>(x->data + x->n_data); }
 struct alignas(64) HostForceMsg {
     int64_t not_before = 0;
     double vn[3] = {0, 0, 0};
@@ -176,6 +198,7 @@ struct PlanCtx {
     std::vector<StrokeRec> strokes;
     int n_stroke_rows = 0, n_stroke_proj = 0;
     std::vector<double> tbuf;
+    uint32_t t_live_tiles = 0;                           // host profiles: tiles the buffer's live track samples intersect
     int t_extent = 0, n_frows = 0, n_prows = 0, n_xfer = 0, xfer_base = 0, chain_obj = -1;
     int rc = 0;
     std::string err;
@@ -194,6 +217,10 @@ public:
     int finalize();
     int build_gq();                                      // closed-form qnorm matrices (once)
     int enqueue_force(int obj, const pbso_force_msg &m, int64_t not_before);
+    // tracks (track_pool.cpp): immutable mono f32 signals in device memory that PBSO_TRACK_FORCE messages play
+    int track_create(const float *samples, int64_t n, int *track_id);
+    int enqueue_track_force(int obj, const pbso_force_msg &m, const pbso_track_play &play, int64_t not_before);
+    void track_stats(int64_t out[4]) const;
     int enqueue_force_batch(int n, const int *objs, const pbso_force_msg *msgs, const int64_t *stamps, unsigned char *accepted);
     int enqueue_vertex_hits(int n, const int *objs, const int *vids, const double *vn, const int64_t *stamps);
     int enqueue_strokes(int n, const int *objs, const int *vids, const double *coords, const double *vn, const int64_t *stamps,
@@ -239,7 +266,15 @@ private:
     int fail(int code, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
     bool valid_obj(int obj) const { return obj >= 0 && obj < (int)objs_.size(); }
-    int enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why);
+    int enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why, const pbso_track_play *play = nullptr,
+                           int64_t track_total = 0);
+    TrackPool *tracks_ = nullptr;                        // created with the first track
+    void track_release();
+    int64_t track_length(int track) const;               // -1: no such track
+    const float *track_device_pool() const;
+    const long long *track_device_table() const;
+    const float *track_host_samples(int track) const;    // engines with host profiles keep a copy
+    std::atomic<int64_t> track_msgs_{0}, track_rows_{0}; // pbso_track_stats [2], [3]
     int alloc_slot(PlanCtx &c);
     void release(PlanCtx &c, ActiveForce &af);
     int plan(int nb);                                    // host bookkeeping for one batch

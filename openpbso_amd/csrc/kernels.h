@@ -198,20 +198,26 @@ struct ArState {         // AutoregressiveForce members that evolve (forces.h:62
     double a[2], sigma, mu;
 };
 struct ProfEntry {       // one active force contributing to one forced buffer's time profile
-    int32_t kind;        // PBSO_POINT_FORCE / PBSO_GAUSSIAN_FORCE / PBSO_AUTOREGRESSIVE_FORCE
+    int32_t kind;        // PBSO_POINT_FORCE / PBSO_GAUSSIAN_FORCE / PBSO_AUTOREGRESSIVE_FORCE / PBSO_TRACK_FORCE
     int32_t state;       // AR: ArState slot
     int32_t flags;       // bit 0: default-construct the AR state first; bit 1: SetParam first
     int32_t count, center, width_samples;     // Gaussian: _count at the start of this buffer
     double a0, a1, sigma, mu;                 // SetParam values (bit 1)
+    // A PBSO_TRACK_FORCE entry uses the same 56 bytes (the stroke kernel writes entries of this layout): state = track id,
+    // flags bit 0 = loop, count = in-buffer index of the buffer's first live sample, center = live samples in this buffer,
+    // a0 = first, a1 = rate, sigma = gain, mu = the BITS of the 64-bit output index k0 of that first live sample (track_k0)
 };
+inline double track_k0_bits(int64_t k0) { double d; static_assert(sizeof(d) == sizeof(k0), ""); __builtin_memcpy(&d, &k0, sizeof(d)); return d; }
 struct ProfRow {         // one dense profile row = one (object, buffer)
     int32_t prow;        // row of the tprof array to write
     int32_t entry_begin, entry_end;
 };
 // chains: rows of one object in buffer order are generated by ONE wave (the AR state is sequential)
 // ar_serial != 0: the AR(2) recurrence as the reference's serial loop (forces.h:107-117) instead of a parallel scan
+// tracks / track_tab: the engine's track pool (f32) and its per-track (offset, length) pairs (Engine::track_create)
 int launch_force_profiles(const int *chain_ptr, int n_chains, const ProfRow *rows, const ProfEntry *entries,
-                          ArState *states, float *tprof, int frames, int b_pad, int ar_serial, int high_prio, hipStream_t stream);
+                          ArState *states, float *tprof, const float *tracks, const long long *track_tab, int frames, int b_pad,
+                          int ar_serial, int high_prio, hipStream_t stream);
 
 // ---- K2, row-parallel form: every row of a launch at once (kernels_exact.hip)
 constexpr int K2_SEG = 1024;     // candidate pairs of a force's engine evaluated by one workgroup of ar_variates_kernel
@@ -237,11 +243,13 @@ struct ArFin { uint32_t x; int32_t saved_available; double saved; };      // per
 int launch_force_rows(const ProfRow *rows, int n_rows, const ProfEntry *entries, const ArUse *uses, int n_uses,
                       const ArStream *streams, const int *seg_stream, int n_segs, int max_segs_per_stream, ArState *states,
                       ArState *snaps, double *vnorm, uint32_t *vstate, int *seg_count, double *cbuf, ArRec *recs, ArFin *fins,
-                      float *tprof, int frames, int b_pad, int c_pitch, bool fused, hipStream_t stream);      // fused: every stream has ONE use -> one launch
+                      float *tprof, const float *tracks, const long long *track_tab, int frames, int b_pad, int c_pitch, bool fused,
+                      hipStream_t stream);      // fused: every stream has ONE use -> one launch
 // ... and, for a one-buffer launch, the fused profile rows AND the combine rows (launch_force_combine's arguments) in one launch
 int launch_force_rows_combine(const ProfRow *rows, int n_rows, const ProfEntry *entries, const ArUse *uses, const ArStream *streams,
                               int max_segs_per_stream, ArState *states, ArState *snaps, double *vnorm, uint32_t *vstate, int *seg_count,
-                              double *cbuf, ArRec *recs, ArFin *fins, float *tprof, int frames, int b_pad, int c_pitch,
+                              double *cbuf, ArRec *recs, ArFin *fins, float *tprof, const float *tracks, const long long *track_tab,
+                              int frames, int b_pad, int c_pitch,
                               const int *row_ptr, const int *slot_idx, const int *row_obj, int n_frows, double *slots, const double *c3,
                               float *grows, const struct ProjectEvent *direct, const double *shapes, const long long *shape_off, const int *n_modes,
                               int m_pad, int n_events, const double *stage, const int *stage_slot, hipStream_t stream);

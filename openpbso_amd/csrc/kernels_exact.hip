@@ -192,9 +192,46 @@ __device__ __forceinline__ uint32_t mulmod31(uint32_t a, uint32_t b) {
 // forces in one buffer) + the new engine state.
 constexpr int K2_THREADS = 256;           // candidate pairs evaluated per batch
 
+// TrackForce::Add (include/openpbso_amd.h, pbso_track_play): output sample k of the play is gain * x(first + rate * (double)k),
+// x the linear interpolation between the two track samples around the read position -- one multiply and one add in fp64 from the
+// 64-bit index, never an accumulated position, so a row depends on (message, buffer) only.  Lanes stride the buffer's live
+// samples; for rates near 1 neighbouring lanes read neighbouring track samples.  The entry's fields: kernels.h, ProfEntry.
+__device__ __forceinline__ void track_add(const ProfEntry &e, const float *__restrict__ tracks, const long long *__restrict__ track_tab,
+                                          double *acc, int frames, int lane) {
+    const float *__restrict__ s = tracks + track_tab[2 * e.state];
+    const long long L = track_tab[2 * e.state + 1];
+    const long long k0 = __double_as_longlong(e.mu);
+    const bool loop = (e.flags & 1) != 0;
+    for (int j = lane; j < e.center; j += K2_THREADS) {
+        const int ii = e.count + j;
+        if (ii >= frames) break;
+        const double p = e.a0 + e.a1 * (double)(k0 + j);
+        double x = 0.0;
+        if (p >= 0.0 && p < 9.0e18) {                                      // (beyond that no int64 holds the index: silence)
+            const double fl = floor(p);
+            const double f = p - fl;
+            long long i0 = (long long)fl, i1;
+            double s0 = 0.0, s1 = 0.0;
+            if (loop) {
+                i0 %= L;
+                i1 = i0 + 1 == L ? 0 : i0 + 1;
+                s0 = (double)s[i0];
+                s1 = (double)s[i1];
+            } else {
+                i1 = i0 + 1;
+                if (i0 < L) s0 = (double)s[i0];
+                if (i1 < L) s1 = (double)s[i1];
+            }
+            x = s0 + f * (s1 - s0);
+        }
+        acc[ii] += e.sigma * x;
+    }
+}
+
 __global__ __launch_bounds__(K2_THREADS) void force_profile_kernel(
     const int *__restrict__ chain_ptr, int n_chains, const ProfRow *__restrict__ rows,
     const ProfEntry *__restrict__ entries, ArState *__restrict__ states, float *__restrict__ tprof,
+    const float *__restrict__ tracks, const long long *__restrict__ track_tab,
     int frames, int b_pad, int ar_serial, int high_prio) {
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     switch (high_prio) {
@@ -264,6 +301,8 @@ __global__ __launch_bounds__(K2_THREADS) void force_profile_kernel(
                     const double z = (double)(e.count + ii - e.center) / (double)e.width_samples;
                     acc[ii] += exp(-0.5 * (z * z));
                 }
+            } else if (e.kind == 3) {                                          // TrackForce
+                track_add(e, tracks, track_tab, acc, frames, lane);
             } else {                                                           // AutoregressiveForce, :107-128
                 if (e.state != cached) {                                       // uniform
                     if (cached >= 0 && lane == 0) states[cached] = s;
@@ -492,11 +531,12 @@ __global__ __launch_bounds__(K2_THREADS) void force_profile_kernel(
 }
 
 int launch_force_profiles(const int *chain_ptr, int n_chains, const ProfRow *rows, const ProfEntry *entries,
-                          ArState *states, float *tprof, int frames, int b_pad, int ar_serial, int high_prio, hipStream_t stream) {
+                          ArState *states, float *tprof, const float *tracks, const long long *track_tab, int frames, int b_pad,
+                          int ar_serial, int high_prio, hipStream_t stream) {
     if (n_chains <= 0) return 0;
     const size_t lds = sizeof(double) * (2 * (size_t)frames + 2) + sizeof(uint32_t) * 2 * (K2_THREADS / 64);
     hipLaunchKernelGGL(force_profile_kernel, dim3(n_chains), dim3(K2_THREADS), lds, stream, chain_ptr, n_chains, rows,
-                       entries, states, tprof, frames, b_pad, ar_serial, high_prio);
+                       entries, states, tprof, tracks, track_tab, frames, b_pad, ar_serial, high_prio);
     return (int)hipGetLastError();
 }
 
@@ -829,7 +869,7 @@ __device__ __forceinline__ void force_rows_body(
     const ProfRow *__restrict__ rows, const ProfEntry *__restrict__ entries, const ArUse *__restrict__ uses,
     const ArStream *__restrict__ streams, const ArState *__restrict__ snaps, const ArRec *__restrict__ recs,
     const ArFin *__restrict__ fins, const double *__restrict__ cbuf, ArState *__restrict__ states, float *__restrict__ tprof,
-    int frames, int b_pad, int c_pitch) {
+    const float *__restrict__ tracks, const long long *__restrict__ track_tab, int frames, int b_pad, int c_pitch) {
     double *nrm = k2_lds;
     double *acc = k2_lds + frames;
     const int lane = threadIdx.x, wv = lane >> 6, l64 = lane & 63;
@@ -846,6 +886,8 @@ __device__ __forceinline__ void force_rows_body(
                 const double z = (double)(e.count + ii - e.center) / (double)e.width_samples;
                 acc[ii] += exp(-0.5 * (z * z));
             }
+        } else if (e.kind == 3) {                                          // TrackForce
+            track_add(e, tracks, track_tab, acc, frames, lane);
         } else {                                                           // AutoregressiveForce, :107-128
             const ArUse U = uses[e.count];
             const ArStream S = streams[U.stream];
@@ -898,9 +940,10 @@ __global__ __launch_bounds__(K2_THREADS) void force_rows_kernel(
     const ProfRow *__restrict__ rows, const ProfEntry *__restrict__ entries, const ArUse *__restrict__ uses,
     const ArStream *__restrict__ streams, const ArState *__restrict__ snaps, const ArRec *__restrict__ recs,
     const ArFin *__restrict__ fins, const double *__restrict__ cbuf, ArState *__restrict__ states, float *__restrict__ tprof,
-    int frames, int b_pad, int c_pitch) {
+    const float *__restrict__ tracks, const long long *__restrict__ track_tab, int frames, int b_pad, int c_pitch) {
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
-    force_rows_body((int)blockIdx.x, k2_lds, rows, entries, uses, streams, snaps, recs, fins, cbuf, states, tprof, frames, b_pad, c_pitch);
+    force_rows_body((int)blockIdx.x, k2_lds, rows, entries, uses, streams, snaps, recs, fins, cbuf, states, tprof, tracks, track_tab, frames, b_pad,
+                    c_pitch);
 }
 
 // Round 6: the three kernels above as ONE launch, for launches in which every AutoregressiveForce adds its samples ONCE (one use per
@@ -913,11 +956,12 @@ __device__ __forceinline__ void force_rows_fused_body(
     const ProfRow *__restrict__ rows, const ProfEntry *__restrict__ entries, const ArUse *__restrict__ uses,
     const ArStream *__restrict__ streams, ArState *__restrict__ states, ArState *__restrict__ snaps, double *__restrict__ vnorm,
     uint32_t *__restrict__ vstate, int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs,
-    ArFin *__restrict__ fins, float *__restrict__ tprof, int frames, int b_pad, int c_pitch) {
+    ArFin *__restrict__ fins, float *__restrict__ tprof, const float *__restrict__ tracks, const long long *__restrict__ track_tab,
+    int frames, int b_pad, int c_pitch) {
     const ProfRow row = rows[blockIdx.x];
     for (int ei = row.entry_begin; ei < row.entry_end; ++ei) {
         const ProfEntry e = entries[ei];
-        if (e.kind < 2) continue;                                          // (Point / Gaussian: nothing to prepare)
+        if (e.kind != 2) continue;                                         // (Point / Gaussian / Track: nothing to prepare)
         const int use = e.count;
         const int si = uses[use].stream;
         const ArStream S = streams[si];
@@ -931,18 +975,20 @@ __device__ __forceinline__ void force_rows_fused_body(
         __threadfence();
         __syncthreads();
     }
-    force_rows_body((int)blockIdx.x, k2_lds, rows, entries, uses, streams, snaps, recs, fins, cbuf, states, tprof, frames, b_pad, c_pitch);
+    force_rows_body((int)blockIdx.x, k2_lds, rows, entries, uses, streams, snaps, recs, fins, cbuf, states, tprof, tracks, track_tab, frames, b_pad,
+                    c_pitch);
 }
 __global__ __launch_bounds__(K2_THREADS) void force_rows_fused_kernel(
     const ProfRow *__restrict__ rows, const ProfEntry *__restrict__ entries, const ArUse *__restrict__ uses,
     const ArStream *__restrict__ streams, ArState *__restrict__ states, ArState *__restrict__ snaps, double *__restrict__ vnorm,
     uint32_t *__restrict__ vstate, int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs,
-    ArFin *__restrict__ fins, float *__restrict__ tprof, int frames, int b_pad, int c_pitch) {
+    ArFin *__restrict__ fins, float *__restrict__ tprof, const float *__restrict__ tracks, const long long *__restrict__ track_tab,
+    int frames, int b_pad, int c_pitch) {
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     __shared__ int carry;
-    force_rows_fused_body(k2_lds, cnt, carry, rows, entries, uses, streams, states, snaps, vnorm, vstate, seg_count, cbuf, recs, fins, tprof, frames,
-                          b_pad, c_pitch);
+    force_rows_fused_body(k2_lds, cnt, carry, rows, entries, uses, streams, states, snaps, vnorm, vstate, seg_count, cbuf, recs, fins, tprof, tracks,
+                          track_tab, frames, b_pad, c_pitch);
 }
 
 // The profile rows of a one-buffer launch and its combine rows in ONE launch (round 6, second half): the two touch different arrays --
@@ -967,13 +1013,14 @@ __global__ __launch_bounds__(K2_THREADS) void force_rows_combine_kernel(
     int n_rows, const ProfRow *__restrict__ rows, const ProfEntry *__restrict__ entries, const ArUse *__restrict__ uses,
     const ArStream *__restrict__ streams, ArState *__restrict__ states, ArState *__restrict__ snaps, double *__restrict__ vnorm,
     uint32_t *__restrict__ vstate, int *__restrict__ seg_count, double *__restrict__ cbuf, ArRec *__restrict__ recs,
-    ArFin *__restrict__ fins, float *__restrict__ tprof, int frames, int b_pad, int c_pitch, CombineArgs c) {
+    ArFin *__restrict__ fins, float *__restrict__ tprof, const float *__restrict__ tracks, const long long *__restrict__ track_tab,
+    int frames, int b_pad, int c_pitch, CombineArgs c) {
     extern __shared__ __attribute__((aligned(16))) double k2_lds[];
     __shared__ uint32_t cnt[2][K2_THREADS / 64];
     __shared__ int carry;
     if ((int)blockIdx.x < n_rows) {
         force_rows_fused_body(k2_lds, cnt, carry, rows, entries, uses, streams, states, snaps, vnorm, vstate, seg_count, cbuf, recs, fins, tprof,
-                              frames, b_pad, c_pitch);
+                              tracks, track_tab, frames, b_pad, c_pitch);
     } else {
         force_combine_body(blockIdx.x - (unsigned)n_rows, c.row_ptr, c.slot_idx, c.row_obj, c.slots, c.c3, c.grows, c.direct, c.shapes,
                            c.shape_off, c.n_modes, c.m_pad, c.n_events, c.stage, c.stage_slot, c.slots);
@@ -983,7 +1030,8 @@ static_assert(K2_THREADS == 256, "the combine body's tiles are 256 modes wide");
 
 int launch_force_rows_combine(const ProfRow *rows, int n_rows, const ProfEntry *entries, const ArUse *uses, const ArStream *streams,
                               int max_segs_per_stream, ArState *states, ArState *snaps, double *vnorm, uint32_t *vstate, int *seg_count,
-                              double *cbuf, ArRec *recs, ArFin *fins, float *tprof, int frames, int b_pad, int c_pitch,
+                              double *cbuf, ArRec *recs, ArFin *fins, float *tprof, const float *tracks, const long long *track_tab,
+                              int frames, int b_pad, int c_pitch,
                               const int *row_ptr, const int *slot_idx, const int *row_obj, int n_frows, double *slots, const double *c3,
                               float *grows, const ProjectEvent *direct, const double *shapes, const long long *shape_off, const int *n_modes,
                               int m_pad, int n_events, const double *stage, const int *stage_slot, hipStream_t stream) {
@@ -993,19 +1041,20 @@ int launch_force_rows_combine(const ProfRow *rows, int n_rows, const ProfEntry *
     const size_t lds = std::max(sizeof(double) * (size_t)frames + sizeof(int) * ((size_t)max_segs_per_stream + 2), sizeof(double) * 2 * (size_t)frames);
     CombineArgs c{row_ptr, slot_idx, row_obj, slots, c3, grows, direct, shapes, shape_off, n_modes, m_pad, n_events, stage, stage_slot};
     hipLaunchKernelGGL(force_rows_combine_kernel, dim3((unsigned)wgs), dim3(K2_THREADS), lds, stream, n_rows, rows, entries, uses, streams, states,
-                       snaps, vnorm, vstate, seg_count, cbuf, recs, fins, tprof, frames, b_pad, c_pitch, c);
+                       snaps, vnorm, vstate, seg_count, cbuf, recs, fins, tprof, tracks, track_tab, frames, b_pad, c_pitch, c);
     return (int)hipGetLastError();
 }
 
 int launch_force_rows(const ProfRow *rows, int n_rows, const ProfEntry *entries, const ArUse *uses, int n_uses,
                       const ArStream *streams, const int *seg_stream, int n_segs, int max_segs_per_stream, ArState *states,
                       ArState *snaps, double *vnorm, uint32_t *vstate, int *seg_count, double *cbuf, ArRec *recs, ArFin *fins,
-                      float *tprof, int frames, int b_pad, int c_pitch, bool fused, hipStream_t stream) {
+                      float *tprof, const float *tracks, const long long *track_tab, int frames, int b_pad, int c_pitch, bool fused,
+                      hipStream_t stream) {
     if (n_rows <= 0) return 0;
     if (fused && n_uses > 0) {
         const size_t lds = std::max(sizeof(double) * (size_t)frames + sizeof(int) * ((size_t)max_segs_per_stream + 2), sizeof(double) * 2 * (size_t)frames);
         hipLaunchKernelGGL(force_rows_fused_kernel, dim3(n_rows), dim3(K2_THREADS), lds, stream, rows, entries, uses, streams, states, snaps,
-                           vnorm, vstate, seg_count, cbuf, recs, fins, tprof, frames, b_pad, c_pitch);
+                           vnorm, vstate, seg_count, cbuf, recs, fins, tprof, tracks, track_tab, frames, b_pad, c_pitch);
         return (int)hipGetLastError();
     }
     if (n_segs > 0)
@@ -1017,7 +1066,7 @@ int launch_force_rows(const ProfRow *rows, int n_rows, const ProfEntry *entries,
                            vstate, seg_count, cbuf, recs, fins, frames, c_pitch);
     }
     hipLaunchKernelGGL(force_rows_kernel, dim3(n_rows), dim3(K2_THREADS), sizeof(double) * 2 * (size_t)frames, stream, rows, entries,
-                       uses, streams, snaps, recs, fins, cbuf, states, tprof, frames, b_pad, c_pitch);
+                       uses, streams, snaps, recs, fins, cbuf, states, tprof, tracks, track_tab, frames, b_pad, c_pitch);
     return (int)hipGetLastError();
 }
 

@@ -17,6 +17,7 @@ from . import capi
 POINT_FORCE = capi.POINT_FORCE
 GAUSSIAN_FORCE = capi.GAUSSIAN_FORCE
 AUTOREGRESSIVE_FORCE = capi.AUTOREGRESSIVE_FORCE
+TRACK_FORCE = capi.TRACK_FORCE
 
 
 class PbsoError(RuntimeError):
@@ -384,6 +385,29 @@ class Engine:
         out = (C.c_int64 * 4)()
         self._chk(self._l.pbso_stroke_stats(self._h, out))
         return dict(direct=out[0], queued=out[1], dropped=out[2], kernel_launches=out[3])
+
+    # -- force tracks -----------------------------------------------------------
+    def create_track(self, samples):
+        """pbso_track_create: copy a mono f32 signal into the engine's track pool; returns its id (not a hot-loop call)"""
+        a = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        tid = C.c_int(-1)
+        self._chk(self._l.pbso_track_create(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.size, C.byref(tid)))
+        return tid.value
+
+    def enqueue_track_force(self, obj, msg, track, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sample=0, loop=False,
+                            not_before=0):
+        """pbso_enqueue_track_force: `msg` (its spatial vector and flags; its forceType is set to TRACK_FORCE) plays output
+        samples gain * x(first + rate * k) of `track` from in-buffer sample `start_sample` of the buffer that dequeues it"""
+        m = msg.to_c()
+        m.force_type = capi.TRACK_FORCE
+        p = capi.TrackPlay(int(track), int(bool(loop)), int(start_sample), 0, int(n_samples), float(first), float(rate), float(gain))
+        return bool(self._chk(self._l.pbso_enqueue_track_force(self._h, obj, C.byref(m), C.byref(p), not_before)))
+
+    def track_stats(self):
+        """pbso_track_stats: tracks created, samples held, track-force messages dequeued, profile rows with a track entry"""
+        out = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_track_stats(self._h, out))
+        return tuple(out)
 
     def enqueue_arprm(self, obj, a, sigma, mu, not_before=0):
         a = np.ascontiguousarray(a, dtype=np.float64)

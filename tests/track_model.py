@@ -1,0 +1,359 @@
+"""The fp64 model the track-force tests compare the engine against (the C oracle implements the reference's three force
+types and cannot play a caller's signal).
+
+Two parts:
+ (1) `TrackSolver`: the step bookkeeping of tests/test_oracle_crosschecks.py::PySolver (modal_solver.h:181-276), copied, with a
+     queue limit, the transfer selection and profile closures; `track_profile` implements TrackForce::Add of
+     include/openpbso_amd.h literally -- fp64, no fused multiply-add, v_k = gain * x(first + rate * (double)k).
+ (2) `lfilter_run`: a whole run at once for long scenes: the forcing F[m][t] = c3[m] S_b[m] T_b[t] concatenated over the buffers
+     through scipy.signal.lfilter([1], [1, -c1[m], -c2[m]]), summed with the transfer.
+tests/test_track_model.py anchors both to the C oracle on scripts the oracle can play.
+
+An event is a scenarios.force_ev dict, optionally with "track": dict(track=<index into the scene's track list>, first, rate, gain,
+n_samples, start_sample, loop); or kind "listener" / "use_transfer" as in tests/scenarios.py."""
+import math
+
+import numpy as np
+
+from openpbso_amd import Engine, ForceMessage, capi
+from openpbso_amd.solver import PbsoError
+from oracle import oracle_py as orc
+from tests.scenarios import B, force_ev
+
+class EngineRefused(Exception):
+    """pbso_engine_create or pbso_finalize refused the descriptor (a combination of options the engine does not run)"""
+
+
+QUEUE_SLOTS = 1023
+UNIT_TRANSFER = 1e7
+
+
+# ---------------------------------------------------------------------------
+# profiles: closures that return the buffer's profile, or None when Force::Add returns false
+def point_profile():
+    state = {"used": False}
+
+    def f():
+        if state["used"]:
+            return None
+        state["used"] = True
+        p = np.zeros(B)
+        p[0] = 1.0
+        return p
+    return f
+
+
+def gauss_profile(width_us):
+    w = max(1, int(width_us / 1000000. * 44100))
+    st = {"count": 0, "center": int(4.5 * w)}
+
+    def f():
+        if width_us == 0 or st["count"] >= 10 * w:
+            return None
+        i = np.arange(B)
+        p = np.exp(-0.5 * ((st["count"] + i - st["center"]) / w) ** 2)
+        st["count"] += B
+        return p
+    return f
+
+
+def track_total(L, first, rate, n_samples, loop):
+    """N: how many output samples the play lasts (math.inf: for ever)"""
+    if n_samples > 0:
+        return n_samples
+    if loop:
+        return math.inf
+    if first >= L:
+        return 0
+    n = max(1, int((L - first) / rate))
+    while n > 0 and not (first + rate * float(n - 1) < L):
+        n -= 1
+    while first + rate * float(n) < L:
+        n += 1
+    return n
+
+
+def track_value(s, first, rate, gain, loop, k):
+    """v_k, every operation a separate IEEE double operation (Python floats never fuse)"""
+    L = len(s)
+    p = first + rate * float(k)
+    i = int(math.floor(p))
+    f = p - float(i)
+
+    def S(j):
+        if loop:
+            return float(s[j % L])
+        return float(s[j]) if 0 <= j < L else 0.0
+    s0, s1 = S(i), S(i + 1)
+    return gain * (s0 + f * (s1 - s0))
+
+
+def track_profile(samples, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sample=0, loop=False):
+    s = np.asarray(samples, dtype=np.float32)              # a track is f32 in device memory
+    N = track_total(len(s), first, rate, n_samples, loop)
+    st = {"k0": 0, "o": start_sample}
+
+    def f():
+        if st["k0"] >= N:
+            return None
+        o, k0 = st["o"], st["k0"]
+        p = np.zeros(B)
+        for i in range(o, B):
+            k = k0 + (i - o)
+            if not k < N:
+                break
+            p[i] += track_value(s, first, rate, gain, loop, k)
+        st["k0"] += B - o
+        st["o"] = 0
+        return p
+    f.is_track = True
+    return f
+
+
+# ---------------------------------------------------------------------------
+class TrackSolver:
+    """one ModalSolver<double> (modal_solver.h:181-276), the bookkeeping of PySolver"""
+
+    def __init__(self, c1, c2, c3):
+        self.c1, self.c2, self.c3 = c1, c2, c3
+        self.q1 = np.zeros_like(c1)
+        self.q2 = np.zeros_like(c1)
+        self.queue, self.active, self.sustained = [], [], False
+        self.transfer = np.full_like(c1, UNIT_TRANSFER)
+        self.track_rows = 0                                 # buffers in which a track's Add returned true
+        self.forcing = []                                   # per emitted buffer: (S, T, transfer) for lfilter_run
+
+    def enqueue(self, m):
+        if len(self.queue) >= QUEUE_SLOTS:
+            return False
+        self.queue.append(m)
+        return True
+
+    def bookkeeping(self):
+        """modal_solver.h:184-240: None when the step returns early, else (S, T)"""
+        if self.queue:
+            m = self.queue.pop(0)
+            if m.get("clear"):
+                self.active = []
+                return None
+            if m.get("start"):
+                self.active, self.sustained = [dict(m)], True
+            if not self.sustained:
+                self.active.append(dict(m))
+            else:
+                self.active[0]["data"] = m["data"]
+            if m.get("end"):
+                self.active, self.sustained = [], False
+        T = np.zeros(B)
+        S = np.zeros_like(self.c1)
+        keep = []
+        track_added = False
+        for f in self.active:
+            prof = f["profile"]()                           # the buffer's profile, or None when dead
+            if prof is None and not self.sustained:
+                continue
+            if prof is not None:
+                T += prof
+                track_added = track_added or getattr(f["profile"], "is_track", False)
+            if self.sustained:
+                S = f["data"].copy()
+            else:
+                S += f["data"]
+            keep.append(f)
+        self.active = keep
+        self.track_rows += int(track_added)
+        return S, T
+
+    def samples(self, S, T):
+        """modal_solver.h:258-273: the buffer's samples and its qnorm row, with the transfer in force"""
+        out = np.zeros(B)
+        qn = np.zeros_like(self.c1)
+        for i in range(B):
+            q = (self.c1 * self.q1 + self.c2 * self.q2) + self.c3 * (S * T[i])
+            self.q2, self.q1 = self.q1, q
+            out[i] = float(np.dot(q, self.transfer))
+            qn += q * q
+        return out, np.sqrt(qn)
+
+    def step(self):
+        st = self.bookkeeping()
+        return None if st is None else self.samples(*st)
+
+
+def lfilter_run(c1, c2, c3, forcing):
+    """the emitted buffers `forcing` = [(S, T, transfer)] of a run at once, from rest; returns (audio, qnorm rows, (q1, q2))"""
+    from scipy.signal import lfilter
+    n, nb = len(c1), len(forcing)
+    audio = np.zeros(nb * B)
+    qn = np.zeros((nb, n))
+    q1, q2 = np.zeros(n), np.zeros(n)
+    for m in range(n):
+        F = np.concatenate([c3[m] * (f[0][m] * f[1]) for f in forcing])
+        q = lfilter([1.0], [1.0, -c1[m], -c2[m]], F)
+        audio += q * np.repeat(np.array([f[2][m] for f in forcing]), B)
+        qn[:, m] = np.sqrt((q.reshape(nb, B) ** 2).sum(axis=1))
+        q1[m], q2[m] = q[-1], q[-2]
+    return audio, qn, (q1, q2)
+
+
+# ---------------------------------------------------------------------------
+def track_ev(t, obj, track, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sample=0, loop=False, **force_kw):
+    ev = force_ev(t, obj, force_type=capi.TRACK_FORCE, **force_kw)
+    ev["track"] = dict(track=track, first=first, rate=rate, gain=gain, n_samples=n_samples, start_sample=start_sample, loop=loop)
+    return ev
+
+
+def _data_of(o, ev):
+    n = o.n_modes
+    if ev["data"] is not None:
+        return np.asarray(ev["data"], dtype=np.float64)
+    if ev["vid"] is not None:
+        return orc.modal_force_vertex(o.shapes, ev["vid"], ev["vn"], n)
+    if ev["vids"] is not None:
+        return orc.modal_force_face(o.shapes, ev["vids"], ev["coords"], ev["vn"], n)
+    return np.zeros(n)
+
+
+def _profile_of(ev, tracks):
+    if ev.get("track") is not None:
+        p = dict(ev["track"])
+        return track_profile(tracks[p.pop("track")], **p)
+    if ev["force_type"] == capi.POINT_FORCE:
+        return point_profile()
+    if ev["force_type"] == capi.GAUSSIAN_FORCE:
+        return gauss_profile(ev["width"])
+    raise ValueError("the model plays point, Gaussian and track forces")
+
+
+def model_one(oi, o, tracks, events, n_buffers, per_sample=True):
+    """one object through the model: (audio, emitted, {buffer: qnorm}, (q1, q2), track rows, accepted flags of its force events)"""
+    c1, c2, c3 = orc.iir_coeffs(o.lam, o.rho, o.alpha, o.beta)
+    c1, c2, c3 = c1[:o.n_modes], c2[:o.n_modes], c3[:o.n_modes]
+    s = TrackSolver(c1, c2, c3)
+    helper = None
+    if o.maps is not None:                                   # the transfer vector a listener position selects: the oracle's own lookup
+        from tests.scenarios import _oracle_maps
+        helper = orc.Solver(o.lam, o.rho, o.alpha, o.beta, n_modes=o.n_modes)
+        helper.read_ffat_maps(_oracle_maps(o.maps))
+    use_transfer, queued_transfer = True, None
+    audio = np.zeros(n_buffers * B)
+    emitted = np.ones(n_buffers, dtype=bool)
+    qn, accepted = {}, []
+    evs = sorted([e for e in events if e["obj"] == oi], key=lambda e: e["t"])
+    ei = 0
+    for b in range(n_buffers):
+        while ei < len(evs) and evs[ei]["t"] <= b:
+            ev = evs[ei]
+            ei += 1
+            if ev["kind"] == "force":
+                accepted.append(s.enqueue(dict(data=_data_of(o, ev), profile=None if ev["clear"] else _profile_of(ev, tracks),
+                                               start=ev["start"], end=ev["end"], clear=ev["clear"])))
+            elif ev["kind"] == "listener":
+                if queued_transfer is None:                 # the 1-slot queue: a second position before the step is dropped
+                    helper.compute_transfer(ev["pos"])
+                    helper.step()
+                    queued_transfer = helper.latest_transfer()
+            elif ev["kind"] == "use_transfer":
+                use_transfer = ev["use"]
+            else:
+                raise ValueError(ev["kind"])
+        st = s.bookkeeping()
+        if st is None:
+            emitted[b] = False
+            continue
+        # modal_solver.h:242-256: the transfer is selected behind the force bookkeeping, in front of the samples
+        if use_transfer:
+            if queued_transfer is not None:
+                s.transfer, queued_transfer = queued_transfer, None
+        else:
+            s.transfer = np.full_like(c1, UNIT_TRANSFER)
+        if per_sample:
+            audio[b * B:(b + 1) * B], qn[b] = s.samples(*st)
+        else:
+            s.forcing.append((st[0], st[1], s.transfer.copy()))
+    if not per_sample and s.forcing:
+        keep = np.flatnonzero(emitted)
+        a, rows, (s.q1, s.q2) = lfilter_run(c1, c2, c3, s.forcing)
+        for j, b in enumerate(keep):
+            audio[b * B:(b + 1) * B] = a[j * B:(j + 1) * B]
+            qn[int(b)] = rows[j]
+    if helper is not None:
+        helper.close()
+    return audio, emitted, qn, (s.q1, s.q2), s.track_rows, accepted
+
+
+def run_model(objs, tracks, events, n_buffers, only=None, per_sample=True):
+    """scenarios.run_oracle's outputs from the model, plus track_rows (summed over the objects run) and the accepted flags"""
+    ids = list(range(len(objs))) if only is None else list(only)
+    res = [model_one(oi, objs[oi], tracks, events, n_buffers, per_sample) for oi in ids]
+    return dict(audio=np.array([r[0] for r in res]).reshape(len(ids), n_buffers * B),
+                emitted=np.array([r[1] for r in res]).reshape(len(ids), n_buffers),
+                qnorm={(k, b): v for k, r in enumerate(res) for b, v in r[2].items()}, state=[r[3] for r in res],
+                track_rows=sum(r[4] for r in res), accepted=[r[5] for r in res])
+
+
+# ---------------------------------------------------------------------------
+def message_of(ev):
+    return ForceMessage(data=ev["data"], forceType=ev["force_type"], gaussianWidth=ev["width"], sustainedForceStart=ev["start"],
+                        sustainedForceEnd=ev["end"], clearAllForces=ev["clear"], vid=ev["vid"], vids=ev["vids"], coords=ev["coords"],
+                        vn=ev["vn"])
+
+
+def feed_event(eng, ev, track_ids):
+    """one event into the engine; returns what the enqueue call returned (True for the calls that cannot be refused)"""
+    k = ev["kind"]
+    if k == "force" and ev.get("track") is not None:
+        p = dict(ev["track"])
+        return eng.enqueue_track_force(ev["obj"], message_of(ev), track_ids[p.pop("track")], not_before=ev["t"], **p)
+    if k == "force":
+        return eng.enqueue_force(ev["obj"], message_of(ev), ev["t"])
+    if k == "listener":
+        eng.compute_transfer(ev["obj"], ev["pos"], ev["t"])
+    elif k == "use_transfer":
+        eng.set_use_transfer(ev["obj"], ev["use"], ev["t"])
+    else:
+        raise ValueError(k)
+    return True
+
+
+def run_engine(objs, tracks, events, split, per_step=False, extra=None, **engine_kw):
+    """scenarios.run_engine with tracks: the steps of `split`, the whole script fed before the first step or (per_step) every
+    step its own events just before it; returns audio, emitted, qnorm, state, track_stats, stroke_stats, accepted, info"""
+    try:
+        eng = Engine(**engine_kw)
+    except PbsoError as e:
+        raise EngineRefused(str(e))
+    try:
+        for o in objs:
+            oid = eng.add_object(o.lam, o.rho, o.alpha, o.beta, o.n_modes, o.shapes)
+            if o.maps is not None:
+                eng.set_ffat_maps(oid, o.maps)
+        try:
+            eng.finalize()
+        except PbsoError as e:
+            raise EngineRefused(str(e))
+        ids = [eng.create_track(t) for t in tracks]
+        evs = sorted(events, key=lambda e: e["t"])
+        accepted = []
+        if not per_step:
+            accepted += [feed_event(eng, ev, ids) for ev in evs]
+        if extra is not None:
+            extra(eng, ids)
+        audio, emitted, qn = [], [], {}
+        done = 0
+        for nb in split:
+            if per_step:
+                accepted += [feed_event(eng, ev, ids) for ev in evs if done <= ev["t"] < done + nb]
+            eng.step(nb)
+            audio.append(eng.audio().copy())
+            emitted.append(eng.emitted().copy())
+            if eng.qnorm_mode != capi.QNORM_OFF:
+                for oi in range(len(objs)):
+                    for b in range(nb):
+                        qn[(oi, done + b)] = eng.qnorm(oi, b).copy()
+            done += nb
+        return dict(audio=np.concatenate(audio, axis=1), emitted=np.concatenate(emitted, axis=1).astype(bool), qnorm=qn,
+                    state=[eng.state(i) for i in range(len(objs))], track_stats=eng.track_stats(), stroke_stats=eng.stroke_stats(),
+                    accepted=accepted, info=eng.info())
+    finally:
+        eng.close()

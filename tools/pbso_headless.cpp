@@ -16,6 +16,11 @@
 //                    <buffer> - [start|end]                                              the dummy start / stop message (setZero(N))
 //                    fed one step ahead through pbso_enqueue_strokes (with --devices: to the engines of the ranks);
 //                    --stroke-force point|ar (default ar);  --arprm "<a0> <a1> <sigma> <mu>"  AR parameters from buffer 0 on
+//   --track-hits FILE  hits whose force is a caller-supplied signal (pbso_enqueue_track_force), lines:
+//                    <buffer> <start_sample> <vertex_id> <nx> <ny> <nz> <track file> [gain [rate [first [n_samples [loop]]]]]
+//                    (`-` for the normal as in --hits); the force starts at in-buffer sample <start_sample> of that buffer.  A track
+//                    file is raw little-endian float32 (.f32) or a mono IEEE-float WAV such as this tool writes; every distinct
+//                    path is loaded once.  Composes with --hits (one queue, in buffer order; at equal buffers the --hits line first)
 //   --buffers N      number of 513-sample buffers (default 86 ~ 1 s)
 //   --out FILE       output WAV (default out.wav);  --raw FILE also dumps the fp32 sound values
 //   --devices 0,1,.. several GPUs through the C ABI's device group (one engine per GPU, objects sharded by the sum of their
@@ -77,8 +82,55 @@ static void write_wav_f32(const std::string &path, const std::vector<float> &mon
     std::fclose(f);
 }
 
-struct Hit { long b; pbso_force_msg m; };
+struct Hit { long b; pbso_force_msg m; int track = -1; pbso_track_play play; };   // track >= 0: a --track-hits line, index into the tracks
 struct Pos { long b; double p[3]; };
+// a track file: raw little-endian float32, or a mono IEEE-float WAV (the chunks walked; `fmt ` format 3, 32 bits, one channel)
+static std::vector<float> read_track_file(const std::string &path) {
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) die("cannot read track " + path);
+    std::vector<unsigned char> bytes;
+    unsigned char buf[1 << 16];
+    for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;) bytes.insert(bytes.end(), buf, buf + n);
+    std::fclose(f);
+    size_t off = 0, len = bytes.size();
+    const bool wav = path.size() >= 4 && (path.compare(path.size() - 4, 4, ".wav") == 0 || path.compare(path.size() - 4, 4, ".WAV") == 0);
+    if (wav) {
+        auto u32 = [&](size_t o) { return (uint32_t)bytes[o] | (uint32_t)bytes[o + 1] << 8 | (uint32_t)bytes[o + 2] << 16 | (uint32_t)bytes[o + 3] << 24; };
+        auto u16 = [&](size_t o) { return (unsigned)(bytes[o] | bytes[o + 1] << 8); };
+        if (bytes.size() < 12 || std::memcmp(bytes.data(), "RIFF", 4) != 0 || std::memcmp(bytes.data() + 8, "WAVE", 4) != 0) die("not a WAV file: " + path);
+        bool have_fmt = false, have_data = false;
+        for (size_t o = 12; o + 8 <= bytes.size();) {
+            const size_t n = u32(o + 4);
+            if (o + 8 + n > bytes.size()) die("truncated WAV chunk: " + path);
+            if (std::memcmp(bytes.data() + o, "fmt ", 4) == 0) {
+                if (n < 16 || u16(o + 8) != 3 || u16(o + 10) != 1 || u16(o + 22) != 32) die("track WAV must be mono IEEE float32: " + path);
+                have_fmt = true;
+            } else if (std::memcmp(bytes.data() + o, "data", 4) == 0) {
+                off = o + 8; len = n; have_data = true;
+                break;
+            }
+            o += 8 + n + (n & 1);
+        }
+        if (!have_fmt || !have_data) die("WAV without fmt / data chunk: " + path);
+    }
+    if (len < 4 || len % 4 != 0) die("track file holds no whole float32 samples: " + path);
+    std::vector<float> out(len / 4);
+    std::memcpy(out.data(), bytes.data() + off, len);
+    return out;
+}
+// one message into engine e: a --hits line through pbso_enqueue_force, a --track-hits line with its play record
+static int enqueue_hit(pbso_engine *e, int obj, const Hit &h, const std::vector<int> &track_ids, long stamp) {
+    if (h.track < 0) return pbso_enqueue_force(e, obj, &h.m, stamp);
+    pbso_track_play play = h.play;
+    play.track = track_ids[(size_t)h.track];
+    return pbso_enqueue_track_force(e, obj, &h.m, &play, stamp);
+}
+static std::vector<int> create_tracks(pbso_engine *e, const std::vector<std::vector<float>> &tracks) {
+    std::vector<int> ids(tracks.size(), -1);
+    for (size_t t = 0; t < tracks.size(); ++t) check(e, pbso_track_create(e, tracks[t].data(), (int64_t)tracks[t].size(), &ids[t]), "track_create");
+    return ids;
+}
+
 // --strokes: one entry of the script, and the arrays one pbso_enqueue_strokes call borrows until its step returns
 struct Stroke { long b; unsigned char flags; int v[3]; double c[3], n[3]; };
 struct StrokeFeed {
@@ -141,8 +193,8 @@ struct Scene {
 
 // the scene on several GPUs (include/openpbso_amd.h "device group")
 static int run_group(const std::vector<int> &devices, int copies, int shift, const std::string &modes, const std::string &material,
-                     const std::string &ffat, const std::vector<Hit> &hits, const std::vector<Pos> &path, const StrokeScript &strokes,
-                     int n_buffers, const Scene *scene, std::vector<float> &sound) {
+                     const std::string &ffat, const std::vector<Hit> &hits, const std::vector<std::vector<float>> &tracks,
+                     const std::vector<Pos> &path, const StrokeScript &strokes, int n_buffers, const Scene *scene, std::vector<float> &sound) {
     auto gcheck = [](pbso_group *g, int rc, const char *what) {
         if (rc < 0) die(std::string(what) + ": " + pbso_status_string(rc) + ": " + (g ? pbso_group_last_error(g) : ""));
     };
@@ -184,15 +236,23 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
     pbso_free(om);
     pbso_free(md);
     gcheck(g, pbso_group_finalize(g), "group_finalize");
+    std::vector<std::vector<int>> rank_tracks(devices.size());     // the tracks once per engine that owns a copy
     for (int c = 0; c < copies; ++c) {
         int rank = 0, local = 0;
         gcheck(g, pbso_group_owner(g, c, &rank, &local), "group_owner");
         pbso_engine *e = pbso_group_engine(g, rank);
         if (path.empty()) check(e, pbso_set_use_transfer(e, local, 0, 0), "set_use_transfer");
         for (const Pos &p : path) check(e, pbso_compute_transfer(e, local, p.p, p.b + (long)c * shift), "compute_transfer");
+        if (!tracks.empty() && rank_tracks[rank].empty()) rank_tracks[rank] = create_tracks(e, tracks);
         for (const Hit &h : hits) {
-            const int rc = pbso_group_enqueue_force(g, c, &h.m, h.b + (long)c * shift);
-            gcheck(g, rc, "group_enqueue_force");
+            int rc;
+            if (h.track < 0) {
+                rc = pbso_group_enqueue_force(g, c, &h.m, h.b + (long)c * shift);
+                gcheck(g, rc, "group_enqueue_force");
+            } else {
+                rc = enqueue_hit(e, local, h, rank_tracks[rank], h.b + (long)c * shift);
+                check(e, rc, "enqueue_track_force");
+            }
             if (rc == 0) die("force queue full");
         }
         if (strokes.have_arprm) check(e, pbso_enqueue_arprm(e, local, strokes.arprm, strokes.arprm[2], strokes.arprm[3], (long)c * shift), "enqueue_arprm");
@@ -252,7 +312,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, listener, out = "out.wav", raw, devices_arg, pan, strokes_file, arprm_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, strokes_file, arprm_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
@@ -266,6 +326,7 @@ int main(int argc, char **argv) {
         else if (a == "-t" || a == "--material") material = val();
         else if (a == "-p" || a == "--ffat_map") ffat = val();
         else if (a == "--hits") hits = val();
+        else if (a == "--track-hits") track_hits = val();
         else if (a == "--listener") listener = val();
         else if (a == "--strokes") strokes_file = val();
         else if (a == "--stroke-force") {
@@ -369,6 +430,49 @@ int main(int argc, char **argv) {
             hit_list.push_back(h);
         }
     }
+    std::vector<std::vector<float>> tracks;
+    if (!track_hits.empty()) {
+        std::ifstream f(track_hits);
+        if (!f) die("cannot read " + track_hits);
+        std::vector<std::string> paths;
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            long b; int start, vid; double n[3]; std::string tok, file;
+            if (!(iss >> b >> start >> vid >> tok)) die("bad track-hit line: " + line);
+            if (tok == "-") {
+                if (VN.empty()) die("hit without a normal needs the mesh (-m / -d)");
+                if (vid < 0 || 3 * (size_t)vid + 2 >= VN.size()) die("vertex id out of range: " + line);
+                for (int j = 0; j < 3; ++j) n[j] = VN[3 * (size_t)vid + j];
+            } else {
+                n[0] = std::atof(tok.c_str());
+                if (!(iss >> n[1] >> n[2])) die("bad track-hit line: " + line);
+            }
+            if (!(iss >> file)) die("bad track-hit line (track file): " + line);
+            Hit h;
+            h.b = b;
+            std::memset(&h.m, 0, sizeof(h.m));
+            std::memset(&h.play, 0, sizeof(h.play));
+            h.m.force_type = PBSO_TRACK_FORCE;
+            h.m.data_kind = PBSO_DATA_VERTEX;
+            h.m.vids[0] = vid;
+            const double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            for (int j = 0; j < 3; ++j) h.m.vn[j] = n[j] / len;
+            h.play.start_sample = start;
+            h.play.gain = 1.0; h.play.rate = 1.0;
+            long long ns = 0; int loop = 0;
+            if (iss >> h.play.gain && iss >> h.play.rate && iss >> h.play.first && iss >> ns && iss >> loop) {}
+            h.play.n_samples = ns;
+            h.play.loop = loop;
+            auto at = std::find(paths.begin(), paths.end(), file);
+            h.track = (int)(at - paths.begin());
+            if (at == paths.end()) { paths.push_back(file); tracks.push_back(read_track_file(file)); }
+            hit_list.push_back(h);
+        }
+        // one queue: in buffer order, the --hits line first at equal buffers (a message cannot overtake an earlier one)
+        std::stable_sort(hit_list.begin(), hit_list.end(), [](const Hit &a, const Hit &b) { return a.b < b.b; });
+    }
 
     if (!strokes_file.empty()) {
         std::ifstream f(strokes_file);
@@ -443,7 +547,7 @@ int main(int argc, char **argv) {
     std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
     double device_ms = 0;
     if (!devices.empty()) {
-        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, path, strokes, n_buffers, mixed ? &scene : nullptr, sound);
+        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, sound);
     } else {
         pbso_engine_desc desc;
         std::memset(&desc, 0, sizeof(desc));
@@ -459,9 +563,10 @@ int main(int argc, char **argv) {
         check(e, pbso_finalize(e), "finalize");
         for (const Pos &p : path) check(e, pbso_compute_transfer(e, obj, p.p, p.b), "compute_transfer");
         if (path.empty()) check(e, pbso_set_use_transfer(e, obj, 0, 0), "set_use_transfer");   // unit transfer
+        const std::vector<int> track_ids = create_tracks(e, tracks);
         for (const Hit &h : hit_list) {
-            rc = pbso_enqueue_force(e, obj, &h.m, h.b);
-            check(e, rc, "enqueue_force");
+            rc = enqueue_hit(e, obj, h, track_ids, h.b);
+            check(e, rc, h.track < 0 ? "enqueue_force" : "enqueue_track_force");
             if (rc == 0) die("force queue full");
         }
         if (strokes.have_arprm) check(e, pbso_enqueue_arprm(e, obj, strokes.arprm, strokes.arprm[2], strokes.arprm[3], 0), "enqueue_arprm");
