@@ -473,6 +473,38 @@ int pbso_scene_mix(pbso_engine *e, void *d_out);           /* the last step, asy
 int pbso_read_scene_mix(pbso_engine *e, float *host_out, size_t n);   /* the last mix, synchronously; n = C * n_buffers * B */
 int pbso_scene_mix_reset(pbso_engine *e);
 
+/* Scene filter mix: a second, independent mixer beside the scene mix -- a K-tap FIR per (channel, object) instead of one gain and
+ * delay: a head-related impulse response per ear, an air-absorption filter, a handful of early reflections.
+ *     y_c(t; h, D) = sum_o sum_{k = 0 .. K-1} h_co[k] * x_o(t - D_o - k)
+ *     out_c(t)     = Yfrom_c(t) + w(t) * (Yto_c(t) - Yfrom_c(t))
+ * x_o(i) is object o's audio at absolute sample i across steps, 0 for i < 0; t counts mixed samples from the enable (or the
+ * last reset), 64-bit.  h_co are K f32 taps per (channel, object); D_o is an integer onset per OBJECT, shared by the channels
+ * (interaural delays live in the taps, the onset carries the time of flight).  A set call takes effect at t_set = the first
+ * sample of the next mixed step and cross-fades from the filters and onsets in force (from) to the new ones (to) over
+ * R = xfade_samples: w(t) = (float)((double)(t - t_set + 1) / (double)R) while t - t_set + 1 < R, 1 from then on (at once for
+ * R = 0); once w = 1 only Yto is computed and out = Yto exactly.  The first set after enable / reset takes effect without a
+ * fade; until then the output is silence.  A set that follows another with no mix in between replaces it.  A set while a fade is
+ * still running -- the next mixed sample t has t - t_set + 1 < R -- is PBSO_ERR_STATE (the faded-through filter of two onsets is
+ * not one filter); callers whose steps are at least R samples long never meet this.
+ * Order of arithmetic: per channel and per group of 32 consecutive objects acc = 0.f; objects ascending, taps k = K-1 down to 0,
+ * each acc = fmaf(h[k], x(t - D - k), acc); the groups' results then added in group order starting from 0.f (the order of
+ * pbso_mix_objects and pbso_scene_mix).  Yfrom and Yto are each such a full sum; the blend is three separately rounded f32
+ * operations.  Neither the taps nor a group's objects are split over accumulators summed afterwards, so the output is
+ * bit-reproducible and depends on the rows, the sets and the absolute samples at which they took effect only -- not on how the
+ * samples are cut into steps.  Subnormals are kept.
+ * The last max_onset + K - 1 samples of every object are kept on the device; hence, while this mixer is enabled, every step is
+ * mixed by it exactly once, with the scene mix's error returns: a mix after a step that was not mixed, a second mix of the same
+ * step, or a mix after a step delivered to host memory is PBSO_ERR_STATE.  The reset clears the history and the filters, restarts
+ * t at 0 and arms the mixer for the next step.  The two mixers do not know of each other; both may be enabled.             */
+int pbso_scene_fir_enable(pbso_engine *e, int n_channels, int n_taps, int max_onset, int xfade_samples);  /* after finalize; C 1 .. 8, K 1 .. 1024, max_onset, xfade <= 1 << 20 */
+int pbso_scene_fir_set(pbso_engine *e, const float *taps, const int *onset);  /* taps [C][n_objects][K] (finite); onset [n_objects] in [0, max_onset], NULL = unchanged (0 at first) */
+int pbso_scene_fir(pbso_engine *e, void *d_out);           /* the last step, async on the engine's stream: d_out [C][n_buffers * B] f32, or NULL = engine-owned */
+int pbso_read_scene_fir(pbso_engine *e, float *host_out, size_t n);   /* the last mix, synchronously; n = C * n_buffers * B */
+int pbso_scene_fir_reset(pbso_engine *e);
+/* out[0] = t of the next mixed sample, out[1] = the first t at which the running fade is over (= out[0] when none runs),
+ * out[2] = mixes done, out[3] = set calls accepted */
+int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a
@@ -487,10 +519,13 @@ enum pbso_gather_mode {
     PBSO_GATHER_ROOT = 2,     /* only rank 0 receives them: ncclSend / ncclRecv */
     PBSO_GATHER_MIX = 3,      /* the consumer wants ONE mixed stream: every rank sums its objects' buffers on the device
                                  (pbso_mix_objects) and the ranks all-reduce n_buffers * 513 floats */
-    PBSO_GATHER_SCENE = 4     /* the scene mix: every rank mixes its own objects into C channels (the scene mix above; an empty rank
+    PBSO_GATHER_SCENE = 4,    /* the scene mix: every rank mixes its own objects into C channels (the scene mix above; an empty rank
                                  contributes silence) and the ranks all-reduce C * n_buffers * 513 floats.  While the group's mixer is
                                  enabled, every group step is gathered this way exactly once (a second time: PBSO_ERR_STATE); the
                                  other modes can still be gathered for that step */
+    PBSO_GATHER_FIR = 5       /* the scene filter mix, as PBSO_GATHER_SCENE: every rank filters its own objects (an empty rank contributes
+                                 silence), the ranks all-reduce C * n_buffers * 513 floats; once per step while the group's filter mix is
+                                 enabled */
 };
 #define PBSO_GROUP_ID_BYTES 128
 enum pbso_group_transport {
@@ -542,9 +577,13 @@ int pbso_group_sync(pbso_group *g);
  * its own objects).  After pbso_group_finalize; the arguments as for a single engine.                                       */
 int pbso_group_scene_mix_enable(pbso_group *g, int n_channels, int max_delay, int ramp_samples);
 int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *delay);
+/* the scene filter mix on every local rank; taps [C][n_objects of the whole job][K] and onset [n_objects of the whole job] by
+ * global id.  After pbso_group_finalize; the arguments as for a single engine.                                              */
+int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int max_onset, int xfade_samples);
+int pbso_group_scene_fir_set(pbso_group *g, const float *taps, const int *onset);
 /* the last gather's result on a local rank, a device pointer: ALL -> [world_size * rows_per_rank][n_buffers * 513] (rank r's
  * objects from row r * rows_per_rank; shards smaller than the largest are padded with silent rows), ROOT -> the same on rank 0
- * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE -> [C][n_buffers * 513].  rows / row_floats (may be NULL)
+ * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE and FIR -> [C][n_buffers * 513].  rows / row_floats (may be NULL)
  * receive the shape.                                                                                                        */
 void *pbso_group_result_device_ptr(pbso_group *g, int rank, size_t *rows, size_t *row_floats);
 int pbso_group_read_result(pbso_group *g, int rank, float *host_out, size_t n_floats);   /* that buffer, synchronously */

@@ -30,6 +30,9 @@ EXPORTS = [
     "pbso_step_to_host", "pbso_host_wait", "pbso_host_alloc", "pbso_host_free",
     # the scene mix (C channels, a ramped gain and fractional delay per channel and object)
     "pbso_scene_mix_enable", "pbso_scene_mix_set", "pbso_scene_mix", "pbso_read_scene_mix", "pbso_scene_mix_reset",
+    # the scene filter mix (C channels, K taps per channel and object behind an onset per object)
+    "pbso_scene_fir_enable", "pbso_scene_fir_set", "pbso_scene_fir", "pbso_read_scene_fir", "pbso_scene_fir_reset", "pbso_scene_fir_info",
+    "pbso_group_scene_fir_enable", "pbso_group_scene_fir_set",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -39,7 +42,7 @@ EXPORTS = [
     "pbso_track_create", "pbso_enqueue_track_force", "pbso_track_stats",
 ]
 STROKE_START, STROKE_END, STROKE_ZERO = 1, 2, 4      # pbso_enqueue_strokes flags
-GATHER_ALL, GATHER_ROOT, GATHER_MIX, GATHER_SCENE = 1, 2, 3, 4
+GATHER_ALL, GATHER_ROOT, GATHER_MIX, GATHER_SCENE, GATHER_FIR = 1, 2, 3, 4, 5
 GROUP_ID_BYTES = 128
 
 
@@ -191,6 +194,16 @@ def lib():
     l.pbso_scene_mix_reset.argtypes = [vp]
     l.pbso_group_scene_mix_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     l.pbso_group_scene_mix_set.argtypes = [vp, fp, fp]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_fir"):
+        # (as the tracks above: an older build picked with PBSO_LIB has no filter mix)
+        l.pbso_scene_fir_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        l.pbso_scene_fir_set.argtypes = [vp, fp, ip]
+        l.pbso_scene_fir.argtypes = [vp, vp]
+        l.pbso_read_scene_fir.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_scene_fir_reset.argtypes = [vp]
+        l.pbso_scene_fir_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_group_scene_fir_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        l.pbso_group_scene_fir_set.argtypes = [vp, fp, ip]
     l.pbso_step_to_host.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     l.pbso_host_wait.argtypes = [vp]
     l.pbso_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

@@ -486,6 +486,52 @@ int pbso_scene_mix_reset(pbso_engine *e) {
     GUARD_END(e)
 }
 
+int pbso_scene_fir_enable(pbso_engine *e, int n_channels, int n_taps, int max_onset, int xfade_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_fir_enable(n_channels, n_taps, max_onset, xfade_samples);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_set(pbso_engine *e, const float *taps, const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_set(taps, onset);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir(pbso_engine *e, void *d_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_fir(d_out);
+    GUARD_END(e)
+}
+
+int pbso_read_scene_fir(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_scene_fir(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_fir_reset();
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_info(out);
+    GUARD_END(e)
+}
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

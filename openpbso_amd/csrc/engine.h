@@ -24,6 +24,7 @@
 namespace pbso {
 class SubmitQueue;       // submit_queue.h
 struct SceneMix;         // scene_mix.cpp
+struct SceneFir;         // scene_fir.cpp
 struct TrackPool;        // track_pool.cpp
 
 // ---- growable device / pinned-host buffers ---------------------------------
@@ -240,6 +241,13 @@ public:
     int scene_mix(void *d_out);
     int read_scene_mix(float *out, size_t n);
     int scene_mix_reset();
+    // the scene filter mix (scene_fir.cpp, kernels_fir.hip): C channels, K taps per (channel, object) behind an onset per object
+    int scene_fir_enable(int n_channels, int n_taps, int max_onset, int xfade_samples);
+    int scene_fir_set(const float *taps, const int *onset);
+    int scene_fir(void *d_out);
+    int read_scene_fir(float *out, size_t n);
+    int scene_fir_reset();
+    int scene_fir_info(int64_t out[4]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -473,6 +481,8 @@ private:
     int64_t host_step_ = -1;                             // tot_steps_ of the last pbso_step_to_host (its rows may be in host memory)
     SceneMix *scene_ = nullptr;                          // pbso_scene_mix_enable
     void scene_mix_release();
+    SceneFir *fir_ = nullptr;                            // pbso_scene_fir_enable
+    void scene_fir_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

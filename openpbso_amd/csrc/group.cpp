@@ -102,6 +102,8 @@ struct pbso_group {
     int transport = PBSO_GROUP_RCCL;
     int scene_c = 0, scene_max_delay = 0;                // the scene mixer (pbso_group_scene_mix_enable)
     bool scene_on = false, scene_mixed = false;          // ... and whether the last step has had its PBSO_GATHER_SCENE
+    int fir_c = 0, fir_k = 0, fir_max_onset = 0;         // the scene filter mix (pbso_group_scene_fir_enable)
+    bool fir_on = false, fir_mixed = false;              // ... and whether the last step has had its PBSO_GATHER_FIR
     bool use_rccl = false;                               // a communicator exists: the collectives go through librccl
     bool loopback() const { return transport == PBSO_GROUP_LOOPBACK; }
     std::string err;
@@ -477,6 +479,7 @@ int pbso_group_step(pbso_group *g, int nb) {
     g->slot ^= 1;
     g->stepped = true;
     g->scene_mixed = false;
+    g->fir_mixed = false;
     return PBSO_OK;
 }
 
@@ -524,20 +527,68 @@ int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *dela
     return PBSO_OK;
 }
 
+int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int max_onset, int xfade_samples) {
+    if (!g || !g->finalized) return gfail(g, PBSO_ERR_STATE, "scene_fir_enable before finalize");
+    if (n_channels < 1 || n_channels > pbso::SCENE_MAX_CHANNELS || n_taps < 1 || n_taps > pbso::SCENE_FIR_MAX_TAPS || max_onset < 0 ||
+        max_onset > (1 << 20) || xfade_samples < 0 || xfade_samples > (1 << 20))
+        return gfail(g, PBSO_ERR_INVALID, "scene_fir_enable: n_channels 1 .. 8, n_taps 1 .. 1024, max_onset and xfade_samples 0 .. 1 << 20");
+    for (Rank &rk : g->ranks)                            // (an empty rank has no engine to mix: it contributes silence)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_fir_enable(rk.eng, n_channels, n_taps, max_onset, xfade_samples));
+    g->fir_on = true;
+    g->fir_c = n_channels;
+    g->fir_k = n_taps;
+    g->fir_max_onset = max_onset;
+    g->fir_mixed = true;                                 // (armed for the next step, as every engine is)
+    return PBSO_OK;
+}
+
+int pbso_group_scene_fir_set(pbso_group *g, const float *taps, const int *onset) {
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, "scene_fir_set: the group's scene filter mix is not enabled");
+    if (!taps) return gfail(g, PBSO_ERR_INVALID, "scene_fir_set: taps is NULL");
+    const size_t n = (size_t)g->n_objects, K = (size_t)g->fir_k;
+    // checked for the whole job first: no rank takes a set that another one refuses
+    for (size_t i = 0; i < (size_t)g->fir_c * n * K; ++i)
+        if (!std::isfinite(taps[i])) return gfail(g, PBSO_ERR_INVALID, "scene_fir_set: a tap is not finite");
+    if (onset)
+        for (size_t o = 0; o < n; ++o)
+            if (onset[o] < 0 || onset[o] > g->fir_max_onset) return gfail(g, PBSO_ERR_INVALID, "scene_fir_set: an onset is outside [0, max_onset]");
+    try {
+        std::vector<float> ts;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local;
+            ts.resize((size_t)g->fir_c * nl * K);
+            for (int c = 0; c < g->fir_c; ++c)
+                std::copy(taps + (c * n + lo) * K, taps + (c * n + lo + nl) * K, ts.begin() + c * nl * K);
+            GENG(g, rk, pbso_scene_fir_set(rk.eng, ts.data(), onset ? onset + lo : nullptr));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
+    return PBSO_OK;
+}
+
 // point-to-point transfers in pieces of at most 256 MB: a 1.8 GB ncclSend / ncclRecv pair of a rank to itself (1024 objects x ten seconds
 // of audio) came back WRONG on RCCL 2.26.6 while 0.45 GB was right (profiles/r05 bench_1rank.err); sender and receiver cut alike
 static constexpr size_t P2P_MAX = (size_t)64 << 20;      // floats
 
 int pbso_group_gather(pbso_group *g, int mode) {
     if (!g || !g->stepped) return gfail(g, PBSO_ERR_STATE, "gather before step");
-    if (mode != PBSO_GATHER_ALL && mode != PBSO_GATHER_ROOT && mode != PBSO_GATHER_MIX && mode != PBSO_GATHER_SCENE)
+    if (mode != PBSO_GATHER_ALL && mode != PBSO_GATHER_ROOT && mode != PBSO_GATHER_MIX && mode != PBSO_GATHER_SCENE && mode != PBSO_GATHER_FIR)
         return gfail(g, PBSO_ERR_INVALID, "gather mode");
     const int slot = g->last_slot;
     const size_t row = (size_t)g->last_nb * g->frames, blk = (size_t)g->cmax * row;
-    const size_t scount = (size_t)g->scene_c * row;      // PBSO_GATHER_SCENE: floats of one rank's mix
-    if (mode == PBSO_GATHER_SCENE) {
-        if (!g->scene_on) return gfail(g, PBSO_ERR_STATE, "scene gather: the group's scene mixer is not enabled");
-        if (g->scene_mixed) return gfail(g, PBSO_ERR_STATE, "scene gather: this step is mixed already (or was taken before the mixer was enabled)");
+    // PBSO_GATHER_SCENE and PBSO_GATHER_FIR share their buffers and their all-reduce: floats of one rank's mix
+    const bool fir = mode == PBSO_GATHER_FIR, scene_like = fir || mode == PBSO_GATHER_SCENE;
+    const size_t scount = (size_t)(fir ? g->fir_c : g->scene_c) * row;
+    if (scene_like) {
+        if (fir) {
+            if (!g->fir_on) return gfail(g, PBSO_ERR_STATE, "filter gather: the group's scene filter mix is not enabled");
+            if (g->fir_mixed) return gfail(g, PBSO_ERR_STATE, "filter gather: this step is mixed already (or was taken before the mixer was enabled)");
+        } else {
+            if (!g->scene_on) return gfail(g, PBSO_ERR_STATE, "scene gather: the group's scene mixer is not enabled");
+            if (g->scene_mixed) return gfail(g, PBSO_ERR_STATE, "scene gather: this step is mixed already (or was taken before the mixer was enabled)");
+        }
         int rc = ensure_scene_buffers(g, scount);
         if (rc != PBSO_OK) return rc;
         for (Rank &rk : g->ranks) {
@@ -545,11 +596,11 @@ int pbso_group_gather(pbso_group *g, int mode) {
             // (the collective that last read this slot's mix is done)
             if (g->loopback()) for (Rank &other : g->ranks) GHIP(g, hipStreamWaitEvent(rk.stream, other.ev_coll[slot], 0));
             else GHIP(g, hipStreamWaitEvent(rk.stream, rk.ev_coll[slot], 0));
-            if (rk.n_local > 0) GENG(g, rk, pbso_scene_mix(rk.eng, rk.scene[slot]));
+            if (rk.n_local > 0) GENG(g, rk, fir ? pbso_scene_fir(rk.eng, rk.scene[slot]) : pbso_scene_mix(rk.eng, rk.scene[slot]));
             else GHIP(g, hipMemsetAsync(rk.scene[slot], 0, scount * sizeof(float), rk.stream));
             GHIP(g, hipEventRecord(rk.ev_step[slot], rk.stream));
         }
-        g->scene_mixed = true;
+        (fir ? g->fir_mixed : g->scene_mixed) = true;
     }
     if (mode == PBSO_GATHER_MIX) {
         for (Rank &rk : g->ranks) {
@@ -576,7 +627,7 @@ int pbso_group_gather(pbso_group *g, int mode) {
                 GNCCL_OPEN(g, g_rccl.AllGather(mine, base, blk, ncclFloat, rk.comm, rk.coll));          // in place: sendbuff == recvbuff + rank * count
             } else if (mode == PBSO_GATHER_MIX) {
                 GNCCL_OPEN(g, g_rccl.AllReduce(rk.mix[slot], rk.mix[slot], row, ncclFloat, ncclSum, rk.comm, rk.coll));
-            } else if (mode == PBSO_GATHER_SCENE) {
+            } else if (scene_like) {
                 GNCCL_OPEN(g, g_rccl.AllReduce(rk.scene[slot], rk.scene[slot], scount, ncclFloat, ncclSum, rk.comm, rk.coll));
             } else if (g->world == 1) {
                 // (PBSO_GROUP_RCCL_ALWAYS: the root's receive and a rank's send, both on the one rank there is -- the rows land in
@@ -613,7 +664,7 @@ int pbso_group_gather(pbso_group *g, int mode) {
                 // (into a row of its own: the other ranks' copies still read this rank's mix row)
                 int lrc = pbso::launch_mix_objects(rows, g->world, (long long)row, (long long)row, parts, loop_mix_out(g, rk, row), rk.coll);
                 if (lrc != 0) return gfail(g, PBSO_ERR_HIP, "loopback all-reduce: launch_mix_objects");
-            } else if (mode == PBSO_GATHER_SCENE) {
+            } else if (scene_like) {
                 // the same for the ranks' C channels, as one row of C * row floats per rank: summed in rank order
                 float *rows = rk.scene_scratch, *parts = rk.scene_scratch + (size_t)g->world * scount;
                 for (Rank &src : g->ranks)
@@ -651,9 +702,10 @@ void *pbso_group_result_device_ptr(pbso_group *g, int rank, size_t *rows, size_t
         if (rows) *rows = 1;
         return g->loopback() ? loop_mix_out(g, *rk, row) : rk->mix[g->last_slot];
     }
-    if (g->last_mode == PBSO_GATHER_SCENE) {
-        if (rows) *rows = (size_t)g->scene_c;
-        return g->loopback() ? scene_loop_out(g, *rk, (size_t)g->scene_c * row) : rk->scene[g->last_slot];
+    if (g->last_mode == PBSO_GATHER_SCENE || g->last_mode == PBSO_GATHER_FIR) {
+        const size_t c = (size_t)(g->last_mode == PBSO_GATHER_FIR ? g->fir_c : g->scene_c);
+        if (rows) *rows = c;
+        return g->loopback() ? scene_loop_out(g, *rk, c * row) : rk->scene[g->last_slot];
     }
     const bool full = g->last_mode == PBSO_GATHER_ALL || (g->last_mode == PBSO_GATHER_ROOT && rk->rank == 0);
     if (rows) *rows = full ? (size_t)g->world * g->cmax : (size_t)g->cmax;

@@ -360,6 +360,20 @@ constexpr int SCENE_MAX_CHANNELS = 8;
 int launch_scene_mix(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const SceneParam *params,
                      int C, int ramp, long long t0, float *parts, float *out, hipStream_t stream);
 
+// pbso_scene_fir (kernels_fir.hip): C output channels, K f32 taps per (channel, object) behind an integer onset per object, as
+// one fmaf chain per (channel, group of 32 objects, sample) on the f32 MFMA; the groups' rows then in group order.
+constexpr int SCENE_FIR_MAX_TAPS = 1024;
+int scene_fir_padded_taps(int K);                        // floats of one (channel, object) row of the padded reversed taps
+// P[n_co][scene_fir_padded_taps(K)] from taps[n_co][K] (n_co = C * n_obj rows)
+int launch_scene_fir_prepare(const float *taps, long long n_co, int K, float *P, hipStream_t stream);
+// out[c][i] = Yto_c(t0 + i), i < n; for i < n_fade (the part of a cross-fade in this step; then R >= 2 and the *_from arrays are
+// read) Yfrom + w (Yto - Yfrom), w = (float)((double)(t0 + i - t_set + 1) / (double)R).  rows [n_obj][n]; hist [n_obj][H] the H
+// samples before it; parts: 2 x C x mix_objects_groups(n_obj) x n floats.  P_to NULL (nothing set yet): silence.  Then hist_next =
+// the last H samples of hist ++ rows.
+int launch_scene_fir(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const float *P_to,
+                     const float *P_from, const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0,
+                     long long t_set, int R, float *parts, float *out, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -147,6 +147,19 @@ class Group:
         assert g.size == self._scene_c * len(self._modes) and (d is None or d.size == g.size)
         self._chk(self._l.pbso_group_scene_mix_set(self._h, g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
 
+    def scene_fir_enable(self, n_channels, n_taps, max_onset, xfade_samples=0):
+        """pbso_group_scene_fir_enable: every group step is then gathered once with GATHER_FIR"""
+        self._chk(self._l.pbso_group_scene_fir_enable(self._h, n_channels, n_taps, max_onset, xfade_samples))
+        self._fir_c, self._fir_k = n_channels, n_taps
+
+    def scene_fir_set(self, taps, onset=None):
+        """pbso_group_scene_fir_set: taps [n_channels][n_objects of the job][n_taps], onset [n_objects of the job] by global id"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        assert h.size == self._fir_c * len(self._modes) * self._fir_k and (d is None or d.size == len(self._modes))
+        self._chk(self._l.pbso_group_scene_fir_set(self._h, h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
     def sync(self):
         self._chk(self._l.pbso_group_sync(self._h))
 

@@ -588,6 +588,40 @@ class Engine:
     def scene_mix_reset(self):
         self._chk(self._l.pbso_scene_mix_reset(self._h))
 
+    # -- scene filter mix: C channels, K taps per (channel, object) behind an integer onset (samples) per object ---------------
+    def scene_fir_enable(self, n_channels, n_taps, max_onset, xfade_samples=0):
+        """pbso_scene_fir_enable: from the next step on, every step is mixed exactly once (scene_fir)"""
+        self._chk(self._l.pbso_scene_fir_enable(self._h, n_channels, n_taps, max_onset, xfade_samples))
+        self._fir_c, self._fir_k, self._fir_nb = n_channels, n_taps, 0
+
+    def scene_fir_set(self, taps, onset=None):
+        """pbso_scene_fir_set: taps [n_channels][n_objects][n_taps], onset [n_objects] ints; onset None keeps the onsets"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        assert h.size == self._fir_c * len(self.n_modes) * self._fir_k and (d is None or d.size == len(self.n_modes))
+        self._chk(self._l.pbso_scene_fir_set(self._h, h.ctypes.data_as(C.POINTER(C.c_float)),
+                                             None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def scene_fir(self, d_out=None):
+        """pbso_scene_fir: the last step into the device buffer d_out [n_channels][n_buffers * 513] f32 (None: the engine's own)"""
+        self._chk(self._l.pbso_scene_fir(self._h, None if d_out is None else C.c_void_p(d_out)))
+        self._fir_nb = self._last_nb
+
+    def read_scene_fir(self):
+        """the last scene filter mix: [n_channels][n_buffers * 513] float32 (synchronous)"""
+        out = np.empty((self._fir_c, self._fir_nb * self.B), dtype=np.float32)
+        self._chk(self._l.pbso_read_scene_fir(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def scene_fir_reset(self):
+        self._chk(self._l.pbso_scene_fir_reset(self._h))
+
+    def scene_fir_info(self):
+        """pbso_scene_fir_info: t of the next mixed sample, the first t at which the running fade is over, mixes, sets"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_fir_info(self._h, v))
+        return {"t": v[0], "fade_end": v[1], "mixes": v[2], "sets": v[3]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

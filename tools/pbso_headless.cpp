@@ -31,6 +31,11 @@
 //                    mono one: lines <buffer> <copy> <g_0> <d_0> ... <g_{C-1}> <d_{C-1}> set copy's gain and delay (samples) per
 //                    channel from that buffer on, ramped over N samples (default 441); the tool steps the segments between
 //                    these change points, mixes each, and writes a C-channel interleaved float32 WAV (--raw: the same frames)
+//   --channels C --fir FILE [--xfade N]  the same through the scene filter mix (pbso_scene_fir; with --devices PBSO_GATHER_FIR):
+//                    lines <buffer> <copy> <onset> <taps file> give copy a filter per channel behind an onset (samples) from that
+//                    buffer on, cross-faded over N samples (default 441; change points must be at least that far apart).  A taps
+//                    file is raw little-endian float32 [C][K], every file with the same K; every distinct path is loaded once.
+//                    Not together with --pan.
 #include <dirent.h>
 
 #include <algorithm>
@@ -165,13 +170,21 @@ static void feed_strokes(pbso_engine *e, const StrokeScript &sc, const std::vect
 }
 // --channels / --pan: the scene mix's script
 struct Pan { long b; int copy; std::vector<float> gd; };   // gd: g_0 d_0 ... g_{C-1} d_{C-1}
+struct FirLine { long b; int copy, onset, file; };          // file: index into Scene::fir_files
 struct Scene {
     int channels = 0, ramp = 441, copies = 1, max_delay = 0;
     std::vector<Pan> lines;
+    // --fir: the scene filter mix's script instead of the pan script
+    bool fir = false;
+    int xfade = 441, n_taps = 0, max_onset = 0;
+    std::vector<FirLine> fir_lines;
+    std::vector<std::vector<float>> fir_files;           // [C][K] each
     // segments [cuts[k], cuts[k + 1]) between the change points; set_at(b) updates gain / delay [C][copies] for buffer b
     std::vector<int> cuts(int n_buffers) const {
         std::vector<int> c{0, n_buffers};
         for (const Pan &p : lines)
+            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+        for (const FirLine &p : fir_lines)
             if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         std::sort(c.begin(), c.end());
         c.erase(std::unique(c.begin(), c.end()), c.end());
@@ -185,6 +198,19 @@ struct Scene {
                     gain[(size_t)c * copies + p.copy] = p.gd[2 * c];
                     delay[(size_t)c * copies + p.copy] = p.gd[2 * c + 1];
                 }
+                any = true;
+            }
+        return any;
+    }
+    // ... and taps [C][copies][K], onset [copies]
+    bool fir_set_at(long b, std::vector<float> &taps, std::vector<int> &onset) const {
+        bool any = false;
+        for (const FirLine &p : fir_lines)
+            if (p.b == b) {
+                for (int c = 0; c < channels; ++c)
+                    std::copy(fir_files[p.file].begin() + (size_t)c * n_taps, fir_files[p.file].begin() + (size_t)(c + 1) * n_taps,
+                              taps.begin() + ((size_t)c * copies + p.copy) * n_taps);
+                onset[p.copy] = p.onset;
                 any = true;
             }
         return any;
@@ -276,17 +302,22 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         // the segments between the pan script's change points, each gathered as a C-channel scene mix: sound [C][n_buffers * B]
         const int C = scene->channels;
         const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
-        gcheck(g, pbso_group_scene_mix_enable(g, C, scene->max_delay, scene->ramp), "group_scene_mix_enable");
+        if (scene->fir) gcheck(g, pbso_group_scene_fir_enable(g, C, scene->n_taps, scene->max_onset, scene->xfade), "group_scene_fir_enable");
+        else gcheck(g, pbso_group_scene_mix_enable(g, C, scene->max_delay, scene->ramp), "group_scene_mix_enable");
         std::vector<float> gain((size_t)C * copies, 0.f), delay((size_t)C * copies, 0.f), seg;
+        std::vector<float> taps(scene->fir ? (size_t)C * copies * scene->n_taps : 0, 0.f);
+        std::vector<int> onset(copies, 0);
         sound.assign((size_t)C * total, 0.f);
         const std::vector<int> cuts = scene->cuts(n_buffers);
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-            if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
+            if (scene->fir) {
+                if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
+            } else if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
             const int nb = cuts[k + 1] - cuts[k];
             const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
             feed_ranks(cuts[k], cuts[k + 1]);
             gcheck(g, pbso_group_step(g, nb), "group_step");
-            gcheck(g, pbso_group_gather(g, PBSO_GATHER_SCENE), "group_gather");
+            gcheck(g, pbso_group_gather(g, scene->fir ? PBSO_GATHER_FIR : PBSO_GATHER_SCENE), "group_gather");
             seg.resize((size_t)C * row);
             gcheck(g, pbso_group_read_result(g, 0, seg.data(), seg.size()), "group_read_result");
             for (int c = 0; c < C; ++c)
@@ -312,7 +343,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, strokes_file, arprm_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, strokes_file, arprm_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
@@ -345,6 +376,8 @@ int main(int argc, char **argv) {
         else if (a == "--channels") scene.channels = std::atoi(val().c_str());
         else if (a == "--pan") pan = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
+        else if (a == "--fir") fir = val();
+        else if (a == "--xfade") scene.xfade = std::atoi(val().c_str());
         else die("unknown flag " + a);
     }
     if (!d.empty()) {                                   // fixed directory structure, tools/...:480-495
@@ -516,11 +549,51 @@ int main(int argc, char **argv) {
         if (devices.empty()) die("--devices needs a list of HIP ordinals");
         if (copies <= 0) copies = (int)devices.size();
     }
-    const bool mixed = scene.channels != 0 || !pan.empty();
-    if (mixed) {
+    const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
+    if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
+    if (mixed && (scene.channels < 1 || scene.channels > 8)) die("--channels must be 1 .. 8");
+    if (!fir.empty()) {
+        // the scene filter mix's script: <buffer> <copy> <onset> <taps file>
+        if (scene.xfade < 0 || scene.xfade > (1 << 20)) die("--xfade must be 0 .. 1048576");
+        scene.fir = true;
+        scene.copies = devices.empty() ? 1 : copies;
+        std::ifstream f(fir);
+        if (!f) die("cannot read " + fir);
+        std::vector<std::string> paths;
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            FirLine p;
+            std::string path;
+            if (!(iss >> p.b >> p.copy >> p.onset >> path)) die("bad fir line (<buffer> <copy> <onset> <taps file>): " + line);
+            if (p.copy < 0 || p.copy >= scene.copies) die("fir line for a copy that does not exist: " + line);
+            if (p.b < 0 || p.b >= n_buffers) die("fir line outside buffers 0 .. --buffers - 1: " + line);
+            if (p.onset < 0 || p.onset > (1 << 20)) die("fir onset outside [0, 1048576]: " + line);
+            p.file = (int)(std::find(paths.begin(), paths.end(), path) - paths.begin());
+            if (p.file == (int)paths.size()) {               // a path not seen yet: loaded once
+                paths.push_back(path);
+                std::ifstream tf(path, std::ios::binary);
+                if (!tf) die("cannot read taps file " + path);
+                const std::string bytes((std::istreambuf_iterator<char>(tf)), std::istreambuf_iterator<char>());
+                const size_t per = (size_t)scene.channels * 4;
+                if (bytes.empty() || bytes.size() % per != 0 || bytes.size() / per > 1024)
+                    die("taps file " + path + " is not float32 [--channels][K] with K 1 .. 1024 (" + std::to_string(bytes.size()) + " bytes)");
+                const int K = (int)(bytes.size() / per);
+                if (scene.n_taps != 0 && K != scene.n_taps)
+                    die("taps file " + path + " holds " + std::to_string(K) + " taps per channel, the files before it " + std::to_string(scene.n_taps));
+                scene.n_taps = K;
+                std::vector<float> h((size_t)scene.channels * K);
+                std::memcpy(h.data(), bytes.data(), bytes.size());
+                scene.fir_files.push_back(h);
+            }
+            scene.max_onset = std::max(scene.max_onset, p.onset);
+            scene.fir_lines.push_back(p);
+        }
+        if (scene.fir_lines.empty()) die("no lines in " + fir);
+    } else if (mixed) {
         // the scene mix's script: <buffer> <copy> then a gain and a delay per channel
-        if (scene.channels < 1 || scene.channels > 8) die("--channels must be 1 .. 8");
-        if (pan.empty()) die("--channels needs --pan FILE");
+        if (pan.empty()) die("--channels needs --pan FILE or --fir FILE");
         if (scene.ramp < 0 || scene.ramp > (1 << 20)) die("--ramp must be 0 .. 1048576");
         scene.copies = devices.empty() ? 1 : copies;
         std::ifstream f(pan);
@@ -577,19 +650,29 @@ int main(int argc, char **argv) {
             // the one object through the scene mixer, segment by segment: sound [C][n_buffers * B]
             const int C = scene.channels;
             const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
-            check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
+            if (scene.fir) check(e, pbso_scene_fir_enable(e, C, scene.n_taps, scene.max_onset, scene.xfade), "scene_fir_enable");
+            else check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
             std::vector<float> gain(C, 0.f), delay(C, 0.f), seg;
+            std::vector<float> taps(scene.fir ? (size_t)C * scene.n_taps : 0, 0.f);
+            std::vector<int> onset(1, 0);
             sound.assign((size_t)C * total, 0.f);
             const std::vector<int> cuts = scene.cuts(n_buffers);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-                if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
+                if (scene.fir) {
+                    if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
+                } else if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
                 const int nb = cuts[k + 1] - cuts[k];
                 const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
                 feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], cuts[k + 1], feed);
                 check(e, pbso_step(e, nb), "step");
-                check(e, pbso_scene_mix(e, nullptr), "scene_mix");
                 seg.resize((size_t)C * row);
-                check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
+                if (scene.fir) {
+                    check(e, pbso_scene_fir(e, nullptr), "scene_fir");
+                    check(e, pbso_read_scene_fir(e, seg.data(), seg.size()), "read_scene_fir");
+                } else {
+                    check(e, pbso_scene_mix(e, nullptr), "scene_mix");
+                    check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
+                }
                 for (int c = 0; c < C; ++c)
                     std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
                               sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
