@@ -505,6 +505,46 @@ int pbso_scene_fir_reset(pbso_engine *e);
  * out[2] = mixes done, out[3] = set calls accepted */
 int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]);
 
+/* Scene reverb: a bus effect behind the mixers -- n_in device-resident signals (a send bus: what pbso_mix_objects, pbso_scene_mix
+ * or pbso_scene_fir just wrote, or some of their channels) convolved with a long impulse response per (output channel, input),
+ * a room's tail of seconds, in the direct form and with the input's history kept across steps.
+ * u_i(t) is input channel i (0 <= i < n_in <= 8) at absolute sample t, 0 for t < 0; t counts processed samples from the enable (or
+ * the last reset), 64-bit; r_ci[k] are K f32 taps per (output channel c, input i), 0 <= c < n_out <= 8, 1 <= K <= 1 << 17.  The
+ * taps are cut into segments of S = PBSO_SCENE_REVERB_SEGMENT = 2048 taps -- S is part of the definition --, J = ceil(K / S)
+ * of them, the last one may be shorter.
+ * Order of arithmetic:
+ *     p_cij(t) : acc = 0.f;  for k = min(K, (j+1) S) - 1 down to j S :  acc = fmaf(r_ci[k], u_i(t - k), acc)
+ *     Y_c(t)   : y = 0.f;    for i ascending, for j ascending :          y = y + p_cij(t)
+ *     out_c(t) = Yfrom_c(t) + w(t) * (Yto_c(t) - Yfrom_c(t))             (three separately rounded operations)
+ *     out_c(t) = add_c(t) + out_c(t)                                     (only when d_add is given; one more rounded add)
+ * The cross-fade follows the rules of the scene filter mix: a set takes effect at t_set = the first sample of the next processed
+ * step; w(t) = (float)((double)(t - t_set + 1) / (double)R) while t - t_set + 1 < R, R = xfade_samples; after that only Yto is
+ * computed and out = Yto exactly.  The first set after enable / reset takes effect without a fade; until then the output is
+ * silence (0.f), or add + 0.f when d_add is given.  A set with no step between it and the previous set replaces it.  A set while a
+ * fade is still running is PBSO_ERR_STATE.
+ * Subnormals are kept.  Nothing else is split over accumulators: the output is bit-reproducible and depends on the input samples,
+ * the sets and the absolute samples at which the sets took effect only -- not on how the samples are cut into steps.  Inputs must
+ * be finite: a non-finite input sample leaves the outputs within K + 15 samples after it unspecified (the kernel multiplies zero
+ * pad taps around every segment with the samples next to its window, and 0 * infinity is NaN).
+ * pbso_scene_reverb processes n = the last step's n_buffers * 513 samples: d_in [n_in][n] f32 on the device, required; d_add
+ * [n_out][n] f32 or NULL, may be the same pointer as d_out (the wet signal added into a dry mix); d_out [n_out][n] f32, or NULL
+ * for an engine-owned buffer, must not overlap d_in.  Asynchronous on the engine's stream: whatever produces d_in must be on that
+ * stream or complete.  The last K - 1 samples of every input channel are kept on the device, double-buffered; hence, while the
+ * reverb is enabled, every step is processed exactly once: a second call for the same step, a call after a step that was skipped
+ * or a call before any step is PBSO_ERR_STATE.  A step delivered to host memory is not an error here: the input is the caller's
+ * buffer.  The reset clears the history and the taps, restarts t at 0 and arms the reverb for the next step.  The reverb knows
+ * nothing of the two mixers; all three may be enabled.  A device group has no reverb: the wet signal of an all-reduced bus is not
+ * the bitwise sum of per-rank wet signals.                                                                                    */
+#define PBSO_SCENE_REVERB_SEGMENT 2048
+int pbso_scene_reverb_enable(pbso_engine *e, int n_in, int n_out, int n_taps, int xfade_samples);   /* after finalize; n_in, n_out 1 .. 8, K 1 .. 1 << 17, xfade <= 1 << 20 */
+int pbso_scene_reverb_set(pbso_engine *e, const float *taps);            /* [n_out][n_in][K], finite */
+int pbso_scene_reverb(pbso_engine *e, const void *d_in, const void *d_add, void *d_out);
+int pbso_read_scene_reverb(pbso_engine *e, float *host_out, size_t n);   /* the last output, synchronously; n = n_out * n_buffers * B */
+int pbso_scene_reverb_reset(pbso_engine *e);
+/* out[0] = t of the next processed sample, out[1] = the first t at which the running fade is over (= out[0] when none runs),
+ * out[2] = steps processed, out[3] = set calls accepted */
+int pbso_scene_reverb_info(pbso_engine *e, int64_t out[4]);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a

@@ -33,6 +33,9 @@ EXPORTS = [
     # the scene filter mix (C channels, K taps per channel and object behind an onset per object)
     "pbso_scene_fir_enable", "pbso_scene_fir_set", "pbso_scene_fir", "pbso_read_scene_fir", "pbso_scene_fir_reset", "pbso_scene_fir_info",
     "pbso_group_scene_fir_enable", "pbso_group_scene_fir_set",
+    # the scene reverb (n_in bus signals through K taps, up to 1 << 17, per output channel and input)
+    "pbso_scene_reverb_enable", "pbso_scene_reverb_set", "pbso_scene_reverb", "pbso_read_scene_reverb", "pbso_scene_reverb_reset",
+    "pbso_scene_reverb_info",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -204,6 +207,13 @@ def lib():
         l.pbso_scene_fir_info.argtypes = [vp, C.POINTER(C.c_int64)]
         l.pbso_group_scene_fir_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         l.pbso_group_scene_fir_set.argtypes = [vp, fp, ip]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_reverb"):
+        l.pbso_scene_reverb_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        l.pbso_scene_reverb_set.argtypes = [vp, fp]
+        l.pbso_scene_reverb.argtypes = [vp, vp, vp, vp]
+        l.pbso_read_scene_reverb.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_scene_reverb_reset.argtypes = [vp]
+        l.pbso_scene_reverb_info.argtypes = [vp, C.POINTER(C.c_int64)]
     l.pbso_step_to_host.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     l.pbso_host_wait.argtypes = [vp]
     l.pbso_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

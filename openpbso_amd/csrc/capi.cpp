@@ -532,6 +532,52 @@ int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_scene_reverb_enable(pbso_engine *e, int n_in, int n_out, int n_taps, int xfade_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_reverb_enable(n_in, n_out, n_taps, xfade_samples);
+    GUARD_END(e)
+}
+
+int pbso_scene_reverb_set(pbso_engine *e, const float *taps) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_reverb_set(taps);
+    GUARD_END(e)
+}
+
+int pbso_scene_reverb(pbso_engine *e, const void *d_in, const void *d_add, void *d_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_reverb(d_in, d_add, d_out);
+    GUARD_END(e)
+}
+
+int pbso_read_scene_reverb(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_scene_reverb(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_scene_reverb_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_reverb_reset();
+    GUARD_END(e)
+}
+
+int pbso_scene_reverb_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_reverb_info(out);
+    GUARD_END(e)
+}
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

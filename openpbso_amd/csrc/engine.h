@@ -25,6 +25,7 @@ namespace pbso {
 class SubmitQueue;       // submit_queue.h
 struct SceneMix;         // scene_mix.cpp
 struct SceneFir;         // scene_fir.cpp
+struct SceneReverb;      // scene_reverb.cpp
 struct TrackPool;        // track_pool.cpp
 
 // ---- growable device / pinned-host buffers ---------------------------------
@@ -248,6 +249,13 @@ public:
     int read_scene_fir(float *out, size_t n);
     int scene_fir_reset();
     int scene_fir_info(int64_t out[4]);
+    // the scene reverb (scene_reverb.cpp, kernels_reverb.hip): a caller's n_in bus signals through K taps per (output channel, input)
+    int scene_reverb_enable(int n_in, int n_out, int n_taps, int xfade_samples);
+    int scene_reverb_set(const float *taps);
+    int scene_reverb(const void *d_in, const void *d_add, void *d_out);
+    int read_scene_reverb(float *out, size_t n);
+    int scene_reverb_reset();
+    int scene_reverb_info(int64_t out[4]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -483,6 +491,8 @@ private:
     void scene_mix_release();
     SceneFir *fir_ = nullptr;                            // pbso_scene_fir_enable
     void scene_fir_release();
+    SceneReverb *reverb_ = nullptr;                      // pbso_scene_reverb_enable
+    void scene_reverb_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

@@ -374,6 +374,23 @@ int launch_scene_fir(const float *rows, int n_obj, long long n, const float *his
                      const float *P_from, const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0,
                      long long t_set, int R, float *parts, float *out, hipStream_t stream);
 
+// pbso_scene_reverb (kernels_reverb.hip): n_in bus signals convolved with K f32 taps per (output channel, input), the taps cut into
+// segments of SCENE_REVERB_SEGMENT: one fmaf chain per (channel, input, segment, sample) on the f32 MFMA, the segments' rows then
+// in (input, segment) order.
+constexpr int SCENE_REVERB_SEGMENT = 2048;               // = PBSO_SCENE_REVERB_SEGMENT: part of the definition
+constexpr int SCENE_REVERB_MAX_TAPS = 1 << 17;
+int scene_reverb_segments(int K);                        // J = ceil(K / segment)
+int scene_reverb_padded_taps(int K);                     // floats of one (channel, input, segment) row of the padded reversed taps
+// P[n_out][n_in][J][scene_reverb_padded_taps(K)] from taps[n_out][n_in][K]
+int launch_scene_reverb_prepare(const float *taps, int n_out, int n_in, int K, float *P, hipStream_t stream);
+// out[c][i] = Yto_c(t0 + i), i < n; for i < n_fade (the part of a cross-fade in this step; then R >= 2 and P_from is read)
+// Yfrom + w (Yto - Yfrom), w = (float)((double)(t0 + i - t_set + 1) / (double)R); then add[c][i] + that when add is given (add may
+// be out).  in [n_in][n]; hist [n_in][K - 1] the samples before it; parts: (n_fade ? 2 : 1) x n_out x n_in J x n floats.  P_to NULL
+// (nothing set yet): silence.  Then hist_next = the last K - 1 samples of hist ++ in.
+int launch_scene_reverb(const float *in, int n_in, long long n, const float *hist, float *hist_next, const float *P_to, const float *P_from,
+                        int n_out, int K, long long n_fade, long long t0, long long t_set, int R, float *parts, const float *add, float *out,
+                        hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -622,6 +622,40 @@ class Engine:
         self._chk(self._l.pbso_scene_fir_info(self._h, v))
         return {"t": v[0], "fade_end": v[1], "mixes": v[2], "sets": v[3]}
 
+    # -- scene reverb: n_in device-resident bus signals through K taps per (output channel, input), history kept across steps ----
+    def scene_reverb_enable(self, n_in, n_out, n_taps, xfade_samples=0):
+        """pbso_scene_reverb_enable: from the next step on, every step is processed exactly once (scene_reverb)"""
+        self._chk(self._l.pbso_scene_reverb_enable(self._h, n_in, n_out, n_taps, xfade_samples))
+        self._rev_shape, self._rev_nb = (n_out, n_in, n_taps), 0
+
+    def scene_reverb_set(self, taps):
+        """pbso_scene_reverb_set: taps [n_out][n_in][n_taps], finite"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        assert h.size == int(np.prod(self._rev_shape))
+        self._chk(self._l.pbso_scene_reverb_set(self._h, h.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_reverb(self, d_in, d_add=None, d_out=None):
+        """pbso_scene_reverb: the device buffer d_in [n_in][n_buffers * 513] f32 of the last step convolved into d_out
+        [n_out][n_buffers * 513] (None: the engine's own), on top of d_add (None: nothing; may be d_out).  Device pointers as integers."""
+        vp = lambda p: None if p is None else C.c_void_p(p)
+        self._chk(self._l.pbso_scene_reverb(self._h, vp(d_in), vp(d_add), vp(d_out)))
+        self._rev_nb = self._last_nb
+
+    def read_scene_reverb(self):
+        """the last scene reverb output: [n_out][n_buffers * 513] float32 (synchronous)"""
+        out = np.empty((self._rev_shape[0], self._rev_nb * self.B), dtype=np.float32)
+        self._chk(self._l.pbso_read_scene_reverb(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def scene_reverb_reset(self):
+        self._chk(self._l.pbso_scene_reverb_reset(self._h))
+
+    def scene_reverb_info(self):
+        """pbso_scene_reverb_info: t of the next processed sample, the first t at which the running fade is over, calls, sets"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_reverb_info(self._h, v))
+        return {"t": v[0], "fade_end": v[1], "calls": v[2], "sets": v[3]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

@@ -36,6 +36,11 @@
 //                    buffer on, cross-faded over N samples (default 441; change points must be at least that far apart).  A taps
 //                    file is raw little-endian float32 [C][K], every file with the same K; every distinct path is loaded once.
 //                    Not together with --pan.
+//   --reverb FILE [--reverb-xfade N]     with --channels C and one of --pan / --fir: the room behind the mix (pbso_scene_reverb).  The
+//                    file is an impulse response per output channel, raw little-endian float32 [C][K], K = file size / 4 C up to
+//                    131072; the send bus is the object mix (pbso_mix_objects, one input), and the WAV is dry + wet: every
+//                    segment's mix goes in as d_add.  N is the reverb's cross-fade length (default 441).  One engine only: not
+//                    with --devices (the wet signal of an all-reduced bus is not the bitwise sum of per-rank wet signals).
 #include <dirent.h>
 
 #include <algorithm>
@@ -179,6 +184,9 @@ struct Scene {
     int xfade = 441, n_taps = 0, max_onset = 0;
     std::vector<FirLine> fir_lines;
     std::vector<std::vector<float>> fir_files;           // [C][K] each
+    // --reverb: an impulse response [C][reverb_taps] behind either mixer
+    std::vector<float> reverb;
+    int reverb_taps = 0, reverb_xfade = 441;
     // segments [cuts[k], cuts[k + 1]) between the change points; set_at(b) updates gain / delay [C][copies] for buffer b
     std::vector<int> cuts(int n_buffers) const {
         std::vector<int> c{0, n_buffers};
@@ -343,7 +351,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, strokes_file, arprm_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, reverb, strokes_file, arprm_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
@@ -378,6 +386,8 @@ int main(int argc, char **argv) {
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else if (a == "--fir") fir = val();
         else if (a == "--xfade") scene.xfade = std::atoi(val().c_str());
+        else if (a == "--reverb") reverb = val();
+        else if (a == "--reverb-xfade") scene.reverb_xfade = std::atoi(val().c_str());
         else die("unknown flag " + a);
     }
     if (!d.empty()) {                                   // fixed directory structure, tools/...:480-495
@@ -617,6 +627,20 @@ int main(int argc, char **argv) {
         }
         scene.max_delay = (int)std::ceil(dmax);
     }
+    if (!reverb.empty()) {
+        if (scene.channels == 0 || (pan.empty() && fir.empty())) die("--reverb needs --channels C and one of --pan FILE or --fir FILE: the wet signal is added to that mix");
+        if (!devices.empty()) die("--reverb runs on one engine, not through a device group (--devices)");
+        if (scene.reverb_xfade < 0 || scene.reverb_xfade > (1 << 20)) die("--reverb-xfade must be 0 .. 1048576");
+        std::ifstream rf(reverb, std::ios::binary);
+        if (!rf) die("cannot read impulse response " + reverb);
+        const std::string bytes((std::istreambuf_iterator<char>(rf)), std::istreambuf_iterator<char>());
+        const size_t per = (size_t)scene.channels * 4;
+        if (bytes.empty() || bytes.size() % per != 0 || bytes.size() / per > (size_t)(1 << 17))
+            die("impulse response " + reverb + " is not float32 [--channels][K] with K 1 .. 131072 (" + std::to_string(bytes.size()) + " bytes)");
+        scene.reverb_taps = (int)(bytes.size() / per);
+        scene.reverb.resize((size_t)scene.channels * scene.reverb_taps);
+        std::memcpy(scene.reverb.data(), bytes.data(), bytes.size());
+    }
     std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
     double device_ms = 0;
     if (!devices.empty()) {
@@ -656,6 +680,15 @@ int main(int argc, char **argv) {
             std::vector<float> taps(scene.fir ? (size_t)C * scene.n_taps : 0, 0.f);
             std::vector<int> onset(1, 0);
             sound.assign((size_t)C * total, 0.f);
+            // --reverb: the mix goes to `dry` and the object mix to `bus`, device-visible memory both, instead of the engine's own
+            // buffers; the reverb reads the bus, adds its result to the dry mix and is what is read back
+            void *dry = nullptr, *bus = nullptr;
+            if (scene.reverb_taps) {
+                if (pbso_host_alloc((size_t)C * total * sizeof(float), &dry) != PBSO_OK || pbso_host_alloc(total * sizeof(float), &bus) != PBSO_OK)
+                    die("cannot allocate the reverb's buffers");
+                check(e, pbso_scene_reverb_enable(e, 1, C, scene.reverb_taps, scene.reverb_xfade), "scene_reverb_enable");
+                check(e, pbso_scene_reverb_set(e, scene.reverb.data()), "scene_reverb_set");
+            }
             const std::vector<int> cuts = scene.cuts(n_buffers);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
                 if (scene.fir) {
@@ -666,17 +699,24 @@ int main(int argc, char **argv) {
                 feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], cuts[k + 1], feed);
                 check(e, pbso_step(e, nb), "step");
                 seg.resize((size_t)C * row);
-                if (scene.fir) {
-                    check(e, pbso_scene_fir(e, nullptr), "scene_fir");
+                if (scene.fir) check(e, pbso_scene_fir(e, dry), "scene_fir");
+                else check(e, pbso_scene_mix(e, dry), "scene_mix");
+                if (scene.reverb_taps) {
+                    check(e, pbso_mix_objects(e, bus), "mix_objects");
+                    check(e, pbso_scene_reverb(e, bus, dry, nullptr), "scene_reverb");
+                    check(e, pbso_read_scene_reverb(e, seg.data(), seg.size()), "read_scene_reverb");
+                } else if (scene.fir) {
                     check(e, pbso_read_scene_fir(e, seg.data(), seg.size()), "read_scene_fir");
                 } else {
-                    check(e, pbso_scene_mix(e, nullptr), "scene_mix");
                     check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
                 }
                 for (int c = 0; c < C; ++c)
                     std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
                               sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
             }
+            if (scene.reverb_taps) check(e, pbso_sync(e), "sync");
+            pbso_host_free(dry);
+            pbso_host_free(bus);
         } else {
             feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
             check(e, pbso_step(e, n_buffers), "step");
