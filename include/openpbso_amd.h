@@ -461,7 +461,15 @@ int pbso_mix_objects(pbso_engine *e, void *d_out);
  * A set call takes effect at t_set = the first sample of the next mixed step and ramps each parameter over R = ramp_samples:
  * p(t) = p_from + (p_to - p_from) (t - t_set + 1) / R until t = t_set + R - 1, p_to from then on (at once for R = 0); a set
  * during a ramp starts from the current value p(t_set - 1); the first set after enable / reset takes effect without a ramp;
- * until then every gain and delay is 0 (silence).  The output depends on the rows, the values set and the absolute samples at
+ * until then every gain and delay is 0 (silence).
+ * Order of arithmetic: the values set are f32, kept as fp64; with k = t - t_set + 1 a ramp is evaluated as p(t) = from + slope * k in
+ * fp64, two rounded operations, slope = (to - from) / R rounded once at the set call (0 for R = 0), and p(t) = to for k >= R.  The gain
+ * is g = (float)p_gain(t).  The delay d = p_delay(t) splits the read position in fp64: fr = d - floor(d), i0 = t - floor(d) - (fr != 0),
+ * f = (float)(1.0 - fr) for fr != 0, else 0.  Then five f32 operations, each rounded, none fused: v = x(i0) + f * (x(i0 + 1) - x(i0))
+ * (v = x(i0) itself when f == 0.f), acc = acc + g * v.  Per channel and per group of 32 consecutive objects acc starts from 0.f and
+ * takes the objects in ascending order; the groups' results are then added in group order starting from 0.f.  Subnormals are kept.
+ * tests/cpp/scene_mix_ref.c states this as plain C, and the device's output equals it bit for bit.  So the output is
+ * bit-reproducible and depends on the rows, the values set and the absolute samples at
  * which they took effect only -- not on how the samples are cut into steps.  The last max_delay + 1 samples of every object
  * are kept on the device, so delays reach back across steps; hence, while the mixer is enabled, every step (pbso_step /
  * pbso_step_into) is mixed exactly once: a mix after a step that was not mixed, a second mix of the same step, or a mix after a
