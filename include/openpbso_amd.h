@@ -553,6 +553,60 @@ int pbso_scene_reverb_reset(pbso_engine *e);
  * out[2] = steps processed, out[3] = set calls accepted */
 int pbso_scene_reverb_info(pbso_engine *e, int64_t out[4]);
 
+/* Master bus: the end of the output chain -- a ramped master gain, a linked look-ahead peak limiter with a hard ceiling, meters per
+ * buffer and 16-bit PCM, on a device buffer [C][n] (what the mixers and the reverb write).  The limiter has no recursion: a sliding
+ * minimum followed by a FIR smoothing of the gain, so it is parallel, bit-reproducible and independent of how the samples are cut
+ * into steps.
+ * Parameters at enable: C channels, 1 .. 8; ceiling T, f32, finite, 0 < T <= 1; look-ahead L, 1 .. 4096; hold H, 0 .. 65536; gain
+ * ramp R <= 1 << 20.  t counts processed samples from the enable (or the last reset), 64-bit; u_c(t) is input channel c, 0 for
+ * t < 0, and must be finite: a non-finite input sample leaves the output unspecified.
+ * Order of arithmetic:
+ *     p(t)    master gain: the scene mix's ramp rule for one parameter (fp64 from + slope * k, slope divided once at the set call),
+ *             initial value 1; a set takes effect at t_set = the first sample of the next processed step and ramps from the value
+ *             in force at t_set - 1 over R samples (at once for R = 0)
+ *     v_c(t)  = (float)p(t) * u_c(t)                                   one rounded f32 multiplication; 0 for t < 0
+ *     pk(t)   = max over c of fabsf(v_c(t))
+ *     r(t)    = pk(t) > T ? T / pk(t) : 1.f                            IEEE f32 division, correctly rounded; 1.f for t < 0
+ *     a(t)    = min over j = 0 .. L + H of r(t - j)
+ *     g(t)    : acc = 0.f; for k = L-1 down to 0: acc = fmaf(w[k], a(t - k), acc);   g = fminf(acc, r(t - L))
+ *     y_c(t)  = fminf(fmaxf(v_c(t - L) * g(t), -T), T)                 one rounded multiplication, then the clamp
+ * The output is the input delayed by L samples.
+ * Smoothing window: L f32 taps, computed once on the host at enable.  In fp64, h_k = 1 - cos(2 pi (k+1) / (L+1)); the sum of the
+ * h_k is taken in ascending k; w[k] = (float)(h_k / sum), so w[0] = 1 for L = 1.  pbso_master_window reads the taps back.
+ * Why it holds: the window of every a(t - k), k = 0 .. L-1, contains sample t - L, so g(t) <= r(t - L) up to the rounding of the
+ * chain, and fminf(acc, r(t - L)) makes that exact.  The f32 taps sum to 1 only up to rounding.  Where the chain over them ends
+ * at or above 1.f (L = 1, 64, 65, 128, 4096 and about half of all L; acc reaches 1.0000001) the fminf gives g = 1.f exactly over
+ * unlimited stretches and the output is the delayed input bit for bit; where it ends below (L = 12 is the first) such stretches
+ * pass at a gain just below 1 (at worst 2.3e-6 below, over all L) and count as limited in the meters.  The final clamp covers
+ * v * fl(T / |v|), which can exceed T by an ulp.  Hence |y_c(t)| <= T for every sample, exactly.
+ * Subnormals are kept.  The device keeps the last 2 L + H samples of every v_c, double-buffered as the reverb's history: all that
+ * r, a and g need.  The output depends only on the input samples, the sets and the absolute samples at which the sets took effect.
+ * pbso_master processes n = the last step's n_buffers * 513 samples: d_in [C][n] f32 on the device, required; d_out [C][n] f32, or
+ * NULL for an engine-owned buffer; d_out == d_in is allowed (d_in is read completely before anything is written).  Asynchronous
+ * on the engine's stream.  While enabled, every step is processed exactly once: a second call for the same step, a call after a
+ * step that was skipped or a call before any step is PBSO_ERR_STATE.  A step delivered to host memory is not an error here: the
+ * input is the caller's buffer.  The reset clears the history, restarts t at 0, keeps the gain last set with its ramp finished
+ * and arms the stage for the next step.  The stage knows nothing of the mixers or the reverb.  A device group has none.
+ * Meters: one record per (buffer b of the call, channel c), [n_buffers][C].  min_gain and n_limited are identical for all c.  */
+typedef struct pbso_master_meter {
+    float in_peak;       /* max |v_c| over the buffer's 513 input samples */
+    float out_peak;      /* max |y_c| over its 513 output samples */
+    float min_gain;      /* min g(t) over them */
+    int32_t n_limited;   /* count of g(t) < 1.f */
+    double sumsq;        /* sum of (double)y * (double)y: each product exact in fp64, the order of the sum is free */
+} pbso_master_meter;     /* 24 bytes */
+int pbso_master_enable(pbso_engine *e, int n_channels, float ceiling, int lookahead, int hold, int ramp_samples);   /* after finalize */
+int pbso_master_set_gain(pbso_engine *e, float gain);                       /* finite */
+int pbso_master(pbso_engine *e, const void *d_in, void *d_out);             /* n = last step's n_buffers * 513; [C][n] f32; d_out NULL = engine-owned; d_out == d_in allowed */
+int pbso_read_master(pbso_engine *e, float *host_out, size_t n);            /* planar [C][n], synchronous; n = C * n_buffers * 513 */
+int pbso_read_master_pcm16(pbso_engine *e, int16_t *host_out, size_t n);    /* interleaved [n][C]: (int16_t)lrintf(y * 32767.f), converted on the device; n as above */
+int pbso_read_master_meters(pbso_engine *e, pbso_master_meter *out, size_t n_records);   /* [n_buffers][C] */
+int pbso_master_window(pbso_engine *e, float *out, size_t n);               /* the L taps in force; n = L */
+int pbso_master_reset(pbso_engine *e);
+/* out[0] = t of the next processed sample, out[1] = the first t at which the gain ramp is over (= out[0] when none runs),
+ * out[2] = steps processed, out[3] = sets accepted */
+int pbso_master_info(pbso_engine *e, int64_t out[4]);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a

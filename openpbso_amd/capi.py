@@ -36,6 +36,9 @@ EXPORTS = [
     # the scene reverb (n_in bus signals through K taps, up to 1 << 17, per output channel and input)
     "pbso_scene_reverb_enable", "pbso_scene_reverb_set", "pbso_scene_reverb", "pbso_read_scene_reverb", "pbso_scene_reverb_reset",
     "pbso_scene_reverb_info",
+    # the master bus (gain, look-ahead limiter, meters and 16-bit PCM on a bus [C][n])
+    "pbso_master_enable", "pbso_master_set_gain", "pbso_master", "pbso_read_master", "pbso_read_master_pcm16",
+    "pbso_read_master_meters", "pbso_master_window", "pbso_master_reset", "pbso_master_info",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -93,6 +96,12 @@ class TrackPlay(C.Structure):
     """pbso_track_play: which part of which track a PBSO_TRACK_FORCE message plays"""
     _fields_ = [("track", C.c_int), ("loop", C.c_int), ("start_sample", C.c_int), ("reserved", C.c_int),
                 ("n_samples", C.c_int64), ("first", C.c_double), ("rate", C.c_double), ("gain", C.c_double)]
+
+
+class MasterMeter(C.Structure):
+    """pbso_master_meter: one record per (buffer, channel) of a pbso_master call, 24 bytes"""
+    _fields_ = [("in_peak", C.c_float), ("out_peak", C.c_float), ("min_gain", C.c_float), ("n_limited", C.c_int32),
+                ("sumsq", C.c_double)]
 
 
 class EngineInfo(C.Structure):
@@ -214,6 +223,16 @@ def lib():
         l.pbso_read_scene_reverb.argtypes = [vp, fp, C.c_size_t]
         l.pbso_scene_reverb_reset.argtypes = [vp]
         l.pbso_scene_reverb_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_master"):
+        l.pbso_master_enable.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+        l.pbso_master_set_gain.argtypes = [vp, C.c_float]
+        l.pbso_master.argtypes = [vp, vp, vp]
+        l.pbso_read_master.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_read_master_pcm16.argtypes = [vp, C.POINTER(C.c_int16), C.c_size_t]
+        l.pbso_read_master_meters.argtypes = [vp, C.POINTER(MasterMeter), C.c_size_t]
+        l.pbso_master_window.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_master_reset.argtypes = [vp]
+        l.pbso_master_info.argtypes = [vp, C.POINTER(C.c_int64)]
     l.pbso_step_to_host.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     l.pbso_host_wait.argtypes = [vp]
     l.pbso_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

@@ -578,6 +578,75 @@ int pbso_scene_reverb_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_master_enable(pbso_engine *e, int n_channels, float ceiling, int lookahead, int hold, int ramp_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->master_enable(n_channels, ceiling, lookahead, hold, ramp_samples);
+    GUARD_END(e)
+}
+
+int pbso_master_set_gain(pbso_engine *e, float gain) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->master_set_gain(gain);
+    GUARD_END(e)
+}
+
+int pbso_master(pbso_engine *e, const void *d_in, void *d_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->master(d_in, d_out);
+    GUARD_END(e)
+}
+
+int pbso_read_master(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_master(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_read_master_pcm16(pbso_engine *e, int16_t *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_master_pcm16(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_read_master_meters(pbso_engine *e, pbso_master_meter *out, size_t n_records) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_master_meters(out, n_records);
+    GUARD_END(e)
+}
+
+int pbso_master_window(pbso_engine *e, float *out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->master_window(out, n);
+    GUARD_END(e)
+}
+
+int pbso_master_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->master_reset();
+    GUARD_END(e)
+}
+
+int pbso_master_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->master_info(out);
+    GUARD_END(e)
+}
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

@@ -26,6 +26,7 @@ class SubmitQueue;       // submit_queue.h
 struct SceneMix;         // scene_mix.cpp
 struct SceneFir;         // scene_fir.cpp
 struct SceneReverb;      // scene_reverb.cpp
+struct Master;           // master.cpp
 struct TrackPool;        // track_pool.cpp
 
 // ---- growable device / pinned-host buffers ---------------------------------
@@ -256,6 +257,16 @@ public:
     int read_scene_reverb(float *out, size_t n);
     int scene_reverb_reset();
     int scene_reverb_info(int64_t out[4]);
+    // the master bus (master.cpp, kernels_master.hip): gain, look-ahead limiter, meters and 16-bit PCM on a caller's bus [C][n]
+    int master_enable(int n_channels, float ceiling, int lookahead, int hold, int ramp_samples);
+    int master_set_gain(float gain);
+    int master(const void *d_in, void *d_out);
+    int read_master(float *out, size_t n);
+    int read_master_pcm16(int16_t *out, size_t n);
+    int read_master_meters(pbso_master_meter *out, size_t n_records);
+    int master_window(float *out, size_t n);
+    int master_reset();
+    int master_info(int64_t out[4]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -493,6 +504,8 @@ private:
     void scene_fir_release();
     SceneReverb *reverb_ = nullptr;                      // pbso_scene_reverb_enable
     void scene_reverb_release();
+    Master *master_ = nullptr;                           // pbso_master_enable
+    void master_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

@@ -391,6 +391,18 @@ int launch_scene_reverb(const float *in, int n_in, long long n, const float *his
                         int n_out, int K, long long n_fade, long long t0, long long t_set, int R, float *parts, const float *add, float *out,
                         hipStream_t stream);
 
+// pbso_master (kernels_master.hip): the master bus on [C][n], n = n_buffers * B.  v = (float)gain(t) * in and r of hist ++ in go to
+// V [C][HL + n] and Rb [HL + n], HL = 2 L + H; the sliding minimum of r by doubling through M0 / M1 [HL + n]; the gains to G [n];
+// out [C][n] (may be in: in is read before anything is written) and meters [n_buffers][C] of pbso_master_meter; then hist_next =
+// the last HL samples of V.  hist [C][HL]; win: the L taps.
+constexpr int MASTER_MAX_LOOKAHEAD = 4096;
+constexpr int MASTER_MAX_HOLD = 65536;
+int launch_master(const float *in, int C, long long n, int B, const float *hist, float *hist_next, int L, int H, float T, SceneParam gain,
+                  int R, long long t0, const float *win, float *V, float *Rb, float *M0, float *M1, float *G, float *out, void *meters,
+                  hipStream_t stream);
+// pcm [n][C] = (int16_t)lrintf(y[c][s] * 32767.f) of y [C][n]
+int launch_master_pcm16(const float *y, int C, long long n, short *pcm, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

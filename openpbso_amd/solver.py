@@ -656,6 +656,56 @@ class Engine:
         self._chk(self._l.pbso_scene_reverb_info(self._h, v))
         return {"t": v[0], "fade_end": v[1], "calls": v[2], "sets": v[3]}
 
+    # -- master bus: gain, look-ahead limiter, meters and 16-bit PCM on a device buffer [C][n], history kept across steps ----------
+    def master_enable(self, n_channels, ceiling, lookahead=64, hold=0, ramp_samples=0):
+        """pbso_master_enable: from the next step on, every step is processed exactly once (master)"""
+        self._chk(self._l.pbso_master_enable(self._h, n_channels, ceiling, lookahead, hold, ramp_samples))
+        self._master_shape, self._master_nb = (n_channels, lookahead), 0
+
+    def master_set_gain(self, gain):
+        """pbso_master_set_gain: takes effect at the first sample of the next processed step, ramped over ramp_samples"""
+        self._chk(self._l.pbso_master_set_gain(self._h, gain))
+
+    def master(self, d_in, d_out=None):
+        """pbso_master: the device buffer d_in [C][n_buffers * 513] f32 of the last step through the gain and the limiter into
+        d_out (None: the engine's own; may be d_in), delayed by the look-ahead.  Device pointers as integers."""
+        vp = lambda p: None if p is None else C.c_void_p(p)
+        self._chk(self._l.pbso_master(self._h, vp(d_in), vp(d_out)))
+        self._master_nb = self._last_nb
+
+    def read_master(self):
+        """the last master output: [C][n_buffers * 513] float32 (synchronous)"""
+        out = np.empty((self._master_shape[0], self._master_nb * self.B), dtype=np.float32)
+        self._chk(self._l.pbso_read_master(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def read_master_pcm16(self):
+        """the last master output as interleaved 16-bit PCM, converted on the device: [n_buffers * 513][C] int16"""
+        out = np.empty((self._master_nb * self.B, self._master_shape[0]), dtype=np.int16)
+        self._chk(self._l.pbso_read_master_pcm16(self._h, out.ctypes.data_as(C.POINTER(C.c_int16)), out.size))
+        return out
+
+    def read_master_meters(self):
+        """the last call's meters: a structured array [n_buffers][C] (in_peak, out_peak, min_gain, n_limited, sumsq)"""
+        out = np.empty((self._master_nb, self._master_shape[0]), dtype=np.dtype(capi.MasterMeter))
+        self._chk(self._l.pbso_read_master_meters(self._h, out.ctypes.data_as(C.POINTER(capi.MasterMeter)), out.size))
+        return out
+
+    def master_window(self):
+        """the L taps of the smoothing window in force, float32"""
+        out = np.empty(self._master_shape[1], dtype=np.float32)
+        self._chk(self._l.pbso_master_window(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def master_reset(self):
+        self._chk(self._l.pbso_master_reset(self._h))
+
+    def master_info(self):
+        """pbso_master_info: t of the next processed sample, the first t at which the gain ramp is over, calls, sets"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_master_info(self._h, v))
+        return {"t": v[0], "ramp_end": v[1], "calls": v[2], "sets": v[3]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

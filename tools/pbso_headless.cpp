@@ -41,6 +41,14 @@
 //                    131072; the send bus is the object mix (pbso_mix_objects, one input), and the WAV is dry + wet: every
 //                    segment's mix goes in as d_add.  N is the reverb's cross-fade length (default 441).  One engine only: not
 //                    with --devices (the wet signal of an all-reduced bus is not the bitwise sum of per-rank wet signals).
+//   --limit T [--lookahead L] [--hold H] [--gain G] [--pcm16]   the master bus (pbso_master) behind whatever the tool would have
+//                    written -- the mono object mix, --pan, --fir, or dry + wet with --reverb: the samples of the WAV without
+//                    --limit times G (default 1) through the look-ahead limiter with ceiling T (0 < T <= 1), look-ahead L
+//                    (default 64, 1 .. 4096) and hold H (default 0).  The limiter delays by L samples: the tool steps ceil(L / 513)
+//                    more buffers with no hits, so that the objects' own tail fills them, and drops the first L output samples:
+//                    the file has the length and alignment of the run without --limit.  --pcm16 writes a 16-bit PCM WAV (format 1)
+//                    converted on the device (pbso_read_master_pcm16); only with --limit.  One engine only: not with --devices;
+//                    not with --raw (the unscaled mix).
 #include <dirent.h>
 
 #include <algorithm>
@@ -89,6 +97,20 @@ static void write_wav_f32(const std::string &path, const std::vector<float> &mon
     std::fwrite(&r, 4, 1, f); std::fwrite(&byte_rate, 4, 1, f); std::fwrite(&align, 2, 1, f); std::fwrite(&bits, 2, 1, f);
     std::fwrite("data", 1, 4, f); std::fwrite(&data_bytes, 4, 1, f);
     std::fwrite(mono.data(), 4, mono.size(), f);
+    std::fclose(f);
+}
+
+static void write_wav_pcm16(const std::string &path, const std::vector<int16_t> &frames, int rate, int channels) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) die("cannot write " + path);
+    const uint32_t data_bytes = (uint32_t)(frames.size() * 2), riff = 36 + data_bytes, fmt_len = 16, byte_rate = rate * 2 * channels;
+    const uint16_t fmt = 1 /* PCM */, ch = (uint16_t)channels, align = (uint16_t)(2 * channels), bits = 16;
+    const uint32_t r = rate;
+    std::fwrite("RIFF", 1, 4, f); std::fwrite(&riff, 4, 1, f); std::fwrite("WAVEfmt ", 1, 8, f);
+    std::fwrite(&fmt_len, 4, 1, f); std::fwrite(&fmt, 2, 1, f); std::fwrite(&ch, 2, 1, f);
+    std::fwrite(&r, 4, 1, f); std::fwrite(&byte_rate, 4, 1, f); std::fwrite(&align, 2, 1, f); std::fwrite(&bits, 2, 1, f);
+    std::fwrite("data", 1, 4, f); std::fwrite(&data_bytes, 4, 1, f);
+    std::fwrite(frames.data(), 2, frames.size(), f);
     std::fclose(f);
 }
 
@@ -355,6 +377,9 @@ int main(int argc, char **argv) {
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
+    bool limit = false, pcm16 = false, master_flag = false;  // --limit; master_flag: one of its companions was given
+    float limit_T = 1.f, master_gain = 1.f;
+    int lookahead = 64, hold = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + a); return argv[++i]; };
@@ -388,7 +413,22 @@ int main(int argc, char **argv) {
         else if (a == "--xfade") scene.xfade = std::atoi(val().c_str());
         else if (a == "--reverb") reverb = val();
         else if (a == "--reverb-xfade") scene.reverb_xfade = std::atoi(val().c_str());
+        else if (a == "--limit") { limit = true; limit_T = (float)std::atof(val().c_str()); }
+        else if (a == "--lookahead") { master_flag = true; lookahead = std::atoi(val().c_str()); }
+        else if (a == "--hold") { master_flag = true; hold = std::atoi(val().c_str()); }
+        else if (a == "--gain") { master_flag = true; master_gain = (float)std::atof(val().c_str()); }
+        else if (a == "--pcm16") pcm16 = true;
         else die("unknown flag " + a);
+    }
+    if (pcm16 && !limit) die("--pcm16 needs --limit T: an integer WAV clips without a ceiling");
+    if (master_flag && !limit) die("--lookahead, --hold and --gain belong to --limit T");
+    if (limit) {
+        if (!devices_arg.empty()) die("--limit runs on one engine, not through a device group (--devices)");
+        if (!raw.empty()) die("--raw dumps the unscaled mix: not with --limit");
+        if (!(std::isfinite(limit_T) && limit_T > 0.f && limit_T <= 1.f)) die("--limit must be a ceiling in (0, 1]");
+        if (lookahead < 1 || lookahead > 4096) die("--lookahead must be 1 .. 4096");
+        if (hold < 0 || hold > 65536) die("--hold must be 0 .. 65536");
+        if (!std::isfinite(master_gain)) die("--gain must be finite");
     }
     if (!d.empty()) {                                   // fixed directory structure, tools/...:480-495
         if (name.empty()) name = guess_name(d);
@@ -642,6 +682,7 @@ int main(int argc, char **argv) {
         std::memcpy(scene.reverb.data(), bytes.data(), bytes.size());
     }
     std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
+    std::vector<int16_t> pcm;                            // --pcm16: the master bus's frames, interleaved, segment behind segment
     double device_ms = 0;
     if (!devices.empty()) {
         run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, sound);
@@ -662,6 +703,7 @@ int main(int argc, char **argv) {
         if (path.empty()) check(e, pbso_set_use_transfer(e, obj, 0, 0), "set_use_transfer");   // unit transfer
         const std::vector<int> track_ids = create_tracks(e, tracks);
         for (const Hit &h : hit_list) {
+            if (limit && h.b >= n_buffers) continue;         // (the tail behind the run: no hits, as the run without --limit has none)
             rc = enqueue_hit(e, obj, h, track_ids, h.b);
             check(e, rc, h.track < 0 ? "enqueue_force" : "enqueue_track_force");
             if (rc == 0) die("force queue full");
@@ -670,10 +712,33 @@ int main(int argc, char **argv) {
         StrokeFeed feed;                                     // (borrowed by the engine until the step that follows returns)
         const std::vector<int> stroke_ids{obj};
         const std::vector<long> stroke_shift{0};
+        // --limit: n_tail more buffers behind the scripts; every segment read back goes, scaled as the WAV would have been, through
+        // the master bus, and what comes out replaces it in `sound` (PCM: in `pcm`, interleaved)
+        const int channels_out = mixed ? scene.channels : 1;
+        const int n_tail = limit ? (lookahead + PBSO_FRAMES_PER_BUFFER - 1) / PBSO_FRAMES_PER_BUFFER : 0, n_run = n_buffers + n_tail;
+        void *m_in = nullptr;
+        if (limit) {
+            if (pbso_host_alloc((size_t)channels_out * n_run * PBSO_FRAMES_PER_BUFFER * sizeof(float), &m_in) != PBSO_OK)
+                die("cannot allocate the master bus's input");
+            check(e, pbso_master_enable(e, channels_out, limit_T, lookahead, hold, 0), "master_enable");
+            check(e, pbso_master_set_gain(e, master_gain), "master_set_gain");
+        }
+        auto master_segment = [&](std::vector<float> &seg) {         // seg [C][row], the last step's
+            float *in = (float *)m_in;
+            for (size_t i = 0; i < seg.size(); ++i) in[i] = (float)((double)seg[i] / 1E10);
+            check(e, pbso_master(e, m_in, nullptr), "master");
+            if (pcm16) {
+                const size_t at = pcm.size();
+                pcm.resize(at + seg.size());
+                check(e, pbso_read_master_pcm16(e, pcm.data() + at, seg.size()), "read_master_pcm16");
+            } else {
+                check(e, pbso_read_master(e, seg.data(), seg.size()), "read_master");
+            }
+        };
         if (mixed) {
             // the one object through the scene mixer, segment by segment: sound [C][n_buffers * B]
             const int C = scene.channels;
-            const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
+            const size_t total = (size_t)n_run * PBSO_FRAMES_PER_BUFFER;
             if (scene.fir) check(e, pbso_scene_fir_enable(e, C, scene.n_taps, scene.max_onset, scene.xfade), "scene_fir_enable");
             else check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
             std::vector<float> gain(C, 0.f), delay(C, 0.f), seg;
@@ -689,14 +754,17 @@ int main(int argc, char **argv) {
                 check(e, pbso_scene_reverb_enable(e, 1, C, scene.reverb_taps, scene.reverb_xfade), "scene_reverb_enable");
                 check(e, pbso_scene_reverb_set(e, scene.reverb.data()), "scene_reverb_set");
             }
-            const std::vector<int> cuts = scene.cuts(n_buffers);
+            std::vector<int> cuts = scene.cuts(n_buffers);
+            if (n_tail) cuts.push_back(n_run);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-                if (scene.fir) {
+                if (cuts[k] >= n_buffers) {
+                    // (--limit's tail: the script ended with the run)
+                } else if (scene.fir) {
                     if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
                 } else if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
                 const int nb = cuts[k + 1] - cuts[k];
                 const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
-                feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], cuts[k + 1], feed);
+                if (cuts[k] < n_buffers) feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], cuts[k + 1], feed);
                 check(e, pbso_step(e, nb), "step");
                 seg.resize((size_t)C * row);
                 if (scene.fir) check(e, pbso_scene_fir(e, dry), "scene_fir");
@@ -710,6 +778,7 @@ int main(int argc, char **argv) {
                 } else {
                     check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
                 }
+                if (limit) master_segment(seg);
                 for (int c = 0; c < C; ++c)
                     std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
                               sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
@@ -718,10 +787,14 @@ int main(int argc, char **argv) {
             pbso_host_free(dry);
             pbso_host_free(bus);
         } else {
+            sound.resize((size_t)n_run * PBSO_FRAMES_PER_BUFFER);
             feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
-            check(e, pbso_step(e, n_buffers), "step");
+            check(e, pbso_step(e, n_run), "step");
             check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
+            if (limit) master_segment(sound);
         }
+        if (limit) check(e, pbso_sync(e), "sync");
+        pbso_host_free(m_in);
         pbso_engine_info info;
         check(e, pbso_get_info(e, &info), "get_info");
         device_ms = mixed ? info.total_device_ms : info.last_step_device_ms;      // (the scene mix steps in segments)
@@ -729,6 +802,22 @@ int main(int argc, char **argv) {
     }
     // C channels interleaved (mono: as it stands)
     const int channels = mixed ? scene.channels : 1;
+    if (limit) {
+        // the master bus's output is in the WAV's scale already; it is L samples late: frames L .. L + n_buffers * 513 are the file
+        const size_t run = sound.size() / channels, keep = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
+        if (pcm16) {
+            write_wav_pcm16(out, std::vector<int16_t>(pcm.begin() + (size_t)lookahead * channels, pcm.begin() + ((size_t)lookahead + keep) * channels),
+                            PBSO_SAMPLE_RATE, channels);
+        } else {
+            std::vector<float> wav(keep * channels);
+            for (size_t i = 0; i < keep; ++i)
+                for (int c = 0; c < channels; ++c) wav[i * channels + c] = sound[(size_t)c * run + lookahead + i];
+            write_wav_f32(out, wav, PBSO_SAMPLE_RATE, channels);
+        }
+        std::printf("%d buffers (%.3f s of audio) in %.3f ms on the device, limited to %g -> %s\n", n_buffers,
+                    n_buffers * (double)PBSO_FRAMES_PER_BUFFER / PBSO_SAMPLE_RATE, device_ms, (double)limit_T, out.c_str());
+        return 0;
+    }
     const size_t frames = sound.size() / channels;
     std::vector<float> frames_raw(sound.size()), wav(sound.size());
     for (size_t i = 0; i < frames; ++i)
