@@ -335,11 +335,6 @@ int Engine::hip_fail(hipError_t e, const char *what) {
     err_ = std::string(what) + ": " + hipGetErrorString(e);
     return PBSO_ERR_HIP;
 }
-#define HIPTRY(expr)                                                   \
-    do {                                                               \
-        hipError_t _e = (expr);                                        \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);              \
-    } while (0)
 #define LAUNCHTRY(expr)                                                \
     do {                                                               \
         int _e = (expr);                                               \

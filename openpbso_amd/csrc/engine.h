@@ -28,6 +28,15 @@ struct SceneFir;         // scene_fir.cpp
 struct SceneReverb;      // scene_reverb.cpp
 struct Master;           // master.cpp
 struct TrackPool;        // track_pool.cpp
+struct BusOut;           // bus_state.h
+struct BusWords;         // bus_clock.h
+
+// inside a member of Engine: a failed HIP call ends it with the call's own text as the message
+#define HIPTRY(expr)                                                   \
+    do {                                                               \
+        hipError_t _e = (expr);                                        \
+        if (_e != hipSuccess) return hip_fail(_e, #expr);              \
+    } while (0)
 
 // ---- growable device / pinned-host buffers ---------------------------------
 template <class T>
@@ -292,6 +301,7 @@ public:
 private:
     int fail(int code, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
+    int read_bus(const BusOut *o, int n_channels, const BusWords &w, float *out, size_t n);   // bus_state.h: the body of the four read_*()
     bool valid_obj(int obj) const { return obj >= 0 && obj < (int)objs_.size(); }
     int enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why, const pbso_track_play *play = nullptr,
                            int64_t track_total = 0);

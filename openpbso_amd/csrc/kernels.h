@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scene_ramp.h"
+
 namespace pbso {
 
 // one audio buffer is processed as tiles of TILE samples; 513 = 19 * 27.
@@ -349,10 +351,8 @@ int launch_copy_rows(const int *src_row, const int *dst_row, int n, double *rows
 int mix_objects_groups(int n_obj);
 int launch_mix_objects(const float *audio, int n_obj, long long stride, long long n, float *parts, float *out, hipStream_t stream);
 
-// pbso_scene_mix (kernels_mix.hip): C output channels, a ramped gain and fractional delay per (channel, object).  One parameter's
-// ramp: p(t) = to once t >= t_set + R - 1 (or R == 0), else from + slope (t - t_set + 1) with slope = (to - from) / R stored
-// by the host, in fp64 (t: absolute sample)
-struct SceneParam { double from, to; long long t_set; double slope; };
+// pbso_scene_mix (kernels_mix.hip): C output channels, a ramped gain and fractional delay per (channel, object), each a
+// SceneParam (scene_ramp.h: the ramp and its evaluation, one definition for host and device)
 constexpr int SCENE_MAX_CHANNELS = 8;
 // out[c][i] = sum_o g_co(t) x_o(t - d_co(t)), t = t0 + i, i < n; params [C][n_obj][2] (gain, delay); rows [n_obj][n] (the step);
 // hist [n_obj][H] the H samples before it.  parts: C x mix_objects_groups(n_obj) x n floats.  Then hist_next = the last H

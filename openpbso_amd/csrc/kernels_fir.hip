@@ -16,6 +16,7 @@
 // denormal flag: subnormal samples come through as fmaf gives them.
 #include <hip/hip_runtime.h>
 
+#include "conv_mfma.h"
 #include "kernels.h"
 
 namespace pbso {
@@ -25,10 +26,6 @@ constexpr int FIR_GROUP = 32;                            // = MIX_GROUP of kerne
 constexpr int FIR_WAVE_TILES = 2;                        // tiles of 256 samples per wave: two independent accumulators per channel
 constexpr int FIR_WAVE_SAMPLES = 256 * FIR_WAVE_TILES;
 constexpr int FIR_STAGE_BATCH = 8;                       // global loads a thread issues before it waits, when staging a window
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// window position i of a strip in LDS: one pad word per 16, so that the 16 blocks a B operand reads at one m lie in 16 banks
-__device__ __forceinline__ int win_at(int i) { return i + (i >> 4); }
 }  // namespace
 
 // P[c][o][LP] = the taps reversed behind 15 zeros and zero-padded: P[15 + j] = h_co[K - 1 - j], so that T[b][m] = P[15 + m - b]
@@ -45,6 +42,8 @@ __global__ __launch_bounds__(256) void fir_prepare_kernel(const float *__restric
 // row -- and its C padded tap rows in LDS once for all channels; every wave then walks the window positions four at a time, one
 // A operand per channel (the taps) and one B operand per tile (the window), 2 C MFMAs per step.
 //   LDS: win [win_at(W)] | taps [C][LP],  W = strip + Mp window positions
+// (The lane decomposition, the batched staging, the two-round walk and the write-out below are the same text in
+//  scene_reverb_stage1 of kernels_reverb.hip -- conv_mfma.h says why they are not shared: an edit here wants the same edit there.)
 template <int C>
 __global__ __launch_bounds__(256) void scene_fir_stage1(const float *__restrict__ rows, int n_obj, long long n, const float *__restrict__ hist,
                                                         int H, const float *__restrict__ P0, const float *__restrict__ P1,
@@ -143,37 +142,13 @@ __global__ __launch_bounds__(256) void scene_fir_stage1(const float *__restrict_
     }
 }
 
-// the groups' partial rows in group order per channel; inside a fade (the step's first n_fade samples) the same sum of the set
-// faded out and out = Yfrom + w (Yto - Yfrom), w = (float)((double)(t - t_set + 1) / (double)R), three rounded operations
+// the groups' partial rows in group order per channel, blended inside a fade (conv_mfma.h; nothing is added: the null folds away)
 __global__ __launch_bounds__(256) void scene_fir_stage2(const float *__restrict__ parts, int C, int n_groups, long long n, long long n_fade,
                                                         long long t0, long long t_set, int R, float *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c = blockIdx.y;
-    const float *p = parts + (long long)c * n_groups * n + i;
-    float yto = 0.f;
-    for (int g = 0; g < n_groups; ++g) yto += p[(long long)g * n];
-    if (i < n_fade) {
-        const float *q = p + (long long)C * n_groups * n;
-        float yfrom = 0.f;
-        for (int g = 0; g < n_groups; ++g) yfrom += q[(long long)g * n];
-        const float w = (float)((double)(t0 + i - t_set + 1) / (double)R);
-        const float d = yto - yfrom;
-        const float wd = w * d;
-        yto = yfrom + wd;
-    }
-    out[(long long)c * n + i] = yto;
+    conv_stage2(parts, C, n_groups, n, n_fade, t0, t_set, R, nullptr, out);
 }
 
-// hist_next[o] = the last H samples of hist[o] ++ rows[o]
-__global__ __launch_bounds__(256) void fir_history_kernel(const float *__restrict__ rows, int n_obj, long long n, const float *__restrict__ hist,
-                                                          float *__restrict__ hist_next, int H) {
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= H) return;
-    const long long j = n + k;                           // index into hist ++ rows
-    for (long long o = blockIdx.y; o < n_obj; o += gridDim.y)
-        hist_next[o * H + k] = j < H ? hist[o * H + j] : rows[o * n + (j - H)];
-}
+PBSO_DEFINE_HISTORY_KERNEL(fir_history_kernel)
 
 int scene_fir_padded_taps(int K) { return (K + 15 + 7) / 8 * 8 + 16; }
 

@@ -26,13 +26,6 @@ namespace {
 constexpr int MS_STRIP = 1024;                           // samples of M a workgroup of the LDS minimum writes
 constexpr int MS_LEVELS = 10;                            // doubling levels it can do: a halo of 2^10 - 1 in front of the strip
 constexpr int GN_WIDE_NS = 4;                            // chains per lane of the wide gain launch (256 lanes: strips of 1024)
-
-// p(t) of the scene mix (kernels_mix.hip), the same expression as the host's
-__device__ __forceinline__ double ramp_value(const SceneParam &p, long long t, int R) {
-    const long long k = t - p.t_set + 1;
-    if (R == 0 || k >= R) return p.to;
-    return p.from + p.slope * (double)k;
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void master_prepare_kernel(const float *__restrict__ in, int C, long long n, const float *__restrict__ hist,

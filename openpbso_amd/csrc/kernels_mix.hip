@@ -10,6 +10,7 @@
 // (parameters constant over a wave's samples) and the per-sample path must round alike.
 #include <hip/hip_runtime.h>
 
+#include "conv_mfma.h"
 #include "kernels.h"
 
 namespace pbso {
@@ -17,12 +18,6 @@ namespace pbso {
 namespace {
 constexpr int SCENE_GROUP = 32;                          // = MIX_GROUP of kernels_exact.hip (mix_objects_groups)
 
-// p(t), with the slope (to - from) / R the host stored at the set call: the same expression as the host's (scene_mix.cpp)
-__device__ __forceinline__ double ramp_value(const SceneParam &p, long long t, int R) {
-    const long long k = t - p.t_set + 1;
-    if (R == 0 || k >= R) return p.to;
-    return p.from + p.slope * (double)k;
-}
 // the read position t - d as i0 + f with i0 = t - off: a fraction of exactly 0 reads x(i0) itself
 __device__ __forceinline__ void delay_split(double d, long long *off, float *f) {
     const double fl = floor(d), fr = d - fl;             // (exact)
@@ -124,15 +119,7 @@ __global__ __launch_bounds__(256) void scene_mix_stage2(const float *__restrict_
     out[(long long)blockIdx.y * n + i] = acc;
 }
 
-// hist_next[o] = the last H samples of hist[o] ++ rows[o]
-__global__ __launch_bounds__(256) void scene_history_kernel(const float *__restrict__ rows, int n_obj, long long n, const float *__restrict__ hist,
-                                                            float *__restrict__ hist_next, int H) {
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= H) return;
-    const long long j = n + k;                           // index into hist ++ rows
-    for (long long o = blockIdx.y; o < n_obj; o += gridDim.y)
-        hist_next[o * H + k] = j < H ? hist[o * H + j] : rows[o * n + (j - H)];
-}
+PBSO_DEFINE_HISTORY_KERNEL(scene_history_kernel)
 
 template <int C>
 static void launch_stage1(long long n, int groups, hipStream_t stream, const float *rows, int n_obj, const float *hist, int H,

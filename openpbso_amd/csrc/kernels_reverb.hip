@@ -15,6 +15,7 @@
 // Built with -ffp-contract=off and without any fast-math or denormal flag.
 #include <hip/hip_runtime.h>
 
+#include "conv_mfma.h"
 #include "kernels.h"
 
 namespace pbso {
@@ -24,10 +25,7 @@ constexpr int S = SCENE_REVERB_SEGMENT;
 constexpr int RV_PIECE = 512;                            // window positions whose taps are in LDS at a time (66 KB a segment at C = 8 otherwise)
 constexpr int RV_TPW = RV_PIECE + 16;                    // floats of one channel's piece
 constexpr int RV_STAGE_BATCH = 8;                        // global loads a thread issues before it waits, when staging
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// window position i of a strip in LDS: one pad word per 16, so that the 16 blocks a B operand reads at one m lie in 16 banks
-__device__ __forceinline__ int win_at(int i) { return i + (i >> 4); }
 __host__ __device__ __forceinline__ int seg_taps(int K, int j) { return K - j * S < S ? K - j * S : S; }
 __host__ __device__ __forceinline__ int seg_positions(int Kj) { return (Kj + 15 + 7) / 8 * 8; }
 }  // namespace
@@ -49,6 +47,8 @@ __global__ __launch_bounds__(256) void reverb_prepare_kernel(const float *__rest
 // LDS once; the C tap rows of the segment follow in pieces of RV_PIECE window positions.  Every wave walks the positions four at a
 // time: one A operand per channel (the taps), one B operand per tile (the window), C T MFMAs on C T accumulators.
 //   LDS: win [win_at(W) + 1] | taps [C][RV_TPW],  W = strip + Mp window positions
+// (The lane decomposition, the batched staging, the two-round walk and the write-out below are the same text in
+//  scene_fir_stage1 of kernels_fir.hip -- conv_mfma.h says why they are not shared: an edit here wants the same edit there.)
 template <int C, int T>
 __global__ __launch_bounds__(256) void scene_reverb_stage1(const float *__restrict__ in, int n_in, long long n, const float *__restrict__ hist,
                                                            int H, const float *__restrict__ P0, const float *__restrict__ P1, int K, int J,
@@ -149,28 +149,10 @@ __global__ __launch_bounds__(256) void scene_reverb_stage1(const float *__restri
     }
 }
 
-// the partial rows in (i, j) order per channel from 0.f; inside a fade (the step's first n_fade samples) the same sum of the set
-// faded out and out = Yfrom + w (Yto - Yfrom), w = (float)((double)(t - t_set + 1) / (double)R), three rounded operations; then
-// add + out when add is given (add may be out: every thread reads its own sample before it writes it).  n_rows = 0: silence.
+// the partial rows in (i, j) order per channel, blended inside a fade, then add + that when add is given (conv_mfma.h)
 __global__ __launch_bounds__(256) void scene_reverb_stage2(const float *__restrict__ parts, int C, int n_rows, long long n, long long n_fade,
                                                            long long t0, long long t_set, int R, const float *add, float *out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c = blockIdx.y;
-    const float *p = parts + (long long)c * n_rows * n + i;
-    float y = 0.f;
-    for (int g = 0; g < n_rows; ++g) y = y + p[(long long)g * n];
-    if (i < n_fade) {
-        const float *q = p + (long long)C * n_rows * n;
-        float yfrom = 0.f;
-        for (int g = 0; g < n_rows; ++g) yfrom = yfrom + q[(long long)g * n];
-        const float w = (float)((double)(t0 + i - t_set + 1) / (double)R);
-        const float d = y - yfrom;
-        const float wd = w * d;
-        y = yfrom + wd;
-    }
-    if (add) y = add[(long long)c * n + i] + y;
-    out[(long long)c * n + i] = y;
+    conv_stage2(parts, C, n_rows, n, n_fade, t0, t_set, R, add, out);
 }
 
 // hist_next[i] = the last H samples of hist[i] ++ in[i]

@@ -1,11 +1,10 @@
 // The engine's side of the master bus (include/openpbso_amd.h "master bus"; kernels_master.hip): the ceiling, the look-ahead and
 // hold, the smoothing window computed once at enable, the gain with its ramp, the history of the last 2 L + H samples of every
 // channel on the device, and the rule that every step is processed exactly once.  Its input is the caller's device buffer, not the
-// step's rows: of a step it reads the length only (last_nb_) and counts steps by tot_steps_.  It knows nothing of the mixers or the
-// reverb.
-#include "engine.h"
+// step's rows: of a step it reads the length only (last_nb_) and counts steps by tot_steps_.  It knows bus_state.h, which holds
+// what the buses have in common (the ramp of one parameter among it), and nothing of the mixers or the reverb.
+#include "bus_state.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -14,86 +13,28 @@ namespace pbso {
 struct Master {
     int C = 0, L = 0, H = 0, R = 0, HL = 0;              // HL = 2 L + H samples of history per channel
     float T = 1.f;
-    SceneParam gain{1.0, 1.0, 0, 0.0};                   // the scene mix's ramp of one parameter; passed to the kernel by value
+    SceneParam gain{1.0, 1.0, 0, 0.0};                   // one ramped parameter (scene_ramp.h); passed to the kernel by value
     std::vector<float> w;                                // the L taps
-    int64_t t = 0;                                       // absolute sample of the next processed step's first sample
-    int64_t next_step = 0;                               // the tot_steps_ the next call must find
+    StepClock clock;
     int64_t n_calls = 0, n_sets = 0;
-    float *hist[2] = {nullptr, nullptr};                 // [C][HL] the samples of v before the next step, double-buffered
-    int cur = 0;
-    float *d_w = nullptr;
-    // work arrays of a call: V [C][HL + n] | Rb, M0, M1 [HL + n] | G [n] in one block; the engine-owned output; meters; PCM
-    float *work = nullptr, *out = nullptr;
-    size_t work_cap = 0, out_cap = 0;
-    pbso_master_meter *meters = nullptr;
-    size_t meters_cap = 0;
-    int16_t *pcm = nullptr;
-    size_t pcm_cap = 0;
-    const float *last_out = nullptr;                     // where the last call wrote
-    int last_nb = 0;
+    HistPair hist;                                       // [C][HL] the samples of v
+    BusOut out;                                          // [C][n]
+    DevMem<float> d_w;
+    DevMem<float> work;                                  // of a call: V [C][HL + n] | Rb, M0, M1 [HL + n] | G [n] in one block
+    DevMem<pbso_master_meter> meters;
+    DevMem<int16_t> pcm;
 
     bool ramping(int64_t at) const { return gain.from != gain.to && at - gain.t_set + 1 < (int64_t)R; }
 };
 
 static_assert(sizeof(pbso_master_meter) == 24, "pbso_master_meter is 24 bytes");
 
-namespace {
-
-// p(t) of include/openpbso_amd.h, in fp64 as the kernel evaluates it (kernels_master.hip)
-double ramp_value(const SceneParam &p, int64_t t, int R) {
-    const int64_t k = t - p.t_set + 1;
-    if (R == 0 || k >= R) return p.to;
-    return p.from + p.slope * (double)k;
-}
-
-void free_master(Master *m) {
-    for (float *h : m->hist)
-        if (h) (void)hipFree(h);
-    if (m->d_w) (void)hipFree(m->d_w);
-    if (m->work) (void)hipFree(m->work);
-    if (m->out) (void)hipFree(m->out);
-    if (m->meters) (void)hipFree(m->meters);
-    if (m->pcm) (void)hipFree(m->pcm);
-    delete m;
-}
-
-// a device buffer of at least n elements; the old block may still be read by a call in flight on the stream
-template <typename E>
-hipError_t grow(E *&p, size_t &cap, size_t n, hipStream_t s) {
-    if (p && n <= cap) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(E));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        return e;
-    }
-    cap = n;
-    return hipSuccess;
-}
-
-}  // namespace
-
-#define HIPTRY(expr)                                                   \
-    do {                                                               \
-        hipError_t _e = (expr);                                        \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);              \
-    } while (0)
-#define GROW(buf, cap, n, what)                                                                                   \
-    do {                                                                                                          \
-        hipError_t _e = grow(buf, cap, n, stream_);                                                               \
-        if (_e != hipSuccess)                                                                                     \
-            return _e == hipErrorOutOfMemory ? fail(PBSO_ERR_NOMEM, what ": cannot allocate") : hip_fail(_e, what); \
-    } while (0)
+static const BusWords WORDS = {"master", "processed", "the master bus", "signal", "processed step", "n_channels"};
 
 void Engine::master_release() {
     if (!master_) return;
     if (stream_) (void)hipStreamSynchronize(stream_);
-    free_master(master_);
+    delete master_;
     master_ = nullptr;
 }
 
@@ -106,7 +47,7 @@ int Engine::master_enable(int C, float T, int L, int H, int ramp) {
     if (ramp < 0 || ramp > (1 << 20)) return fail(PBSO_ERR_INVALID, "master_enable: ramp_samples must be 0 .. 1 << 20");
     HIPTRY(hipSetDevice(desc_.device));
     master_release();
-    Master *m = new Master();
+    std::unique_ptr<Master> m(new Master());
     m->C = C;
     m->T = T;
     m->L = L;
@@ -126,19 +67,14 @@ int Engine::master_enable(int C, float T, int L, int H, int ramp) {
     }
     auto nomem = [&](const char *what) {
         (void)hipGetLastError();
-        free_master(m);
         return fail(PBSO_ERR_NOMEM, std::string("master_enable: cannot allocate ") + what);
     };
-    const size_t hist_bytes = (size_t)C * m->HL * sizeof(float);
-    for (float *&h : m->hist) {
-        if (hipMalloc((void **)&h, hist_bytes) != hipSuccess) { h = nullptr; return nomem("the history"); }
-        if (hipMemsetAsync(h, 0, hist_bytes, stream_) != hipSuccess) return nomem("the history");
-    }
-    if (hipMalloc((void **)&m->d_w, (size_t)L * sizeof(float)) != hipSuccess) { m->d_w = nullptr; return nomem("the window"); }
+    if (m->hist.create((size_t)C * m->HL, stream_) != hipSuccess) return nomem("the history");
+    if (m->d_w.alloc((size_t)L) != hipSuccess) return nomem("the window");
     // (m->w outlives the copy: a Master is freed behind a synchronisation of the stream only)
     if (hipMemcpyAsync(m->d_w, m->w.data(), (size_t)L * sizeof(float), hipMemcpyHostToDevice, stream_) != hipSuccess) return nomem("the window");
-    m->next_step = tot_steps_ + 1;                       // armed for the next step
-    master_ = m;
+    m->clock.arm(tot_steps_);
+    master_ = m.release();
     return PBSO_OK;
 }
 
@@ -147,11 +83,7 @@ int Engine::master_set_gain(float gain) {
     if (!master_) return fail(PBSO_ERR_STATE, "master_set_gain: the master bus is not enabled");
     if (!std::isfinite(gain)) return fail(PBSO_ERR_INVALID, "master_set_gain: the gain is not finite");
     Master &m = *master_;
-    SceneParam &q = m.gain;
-    q.from = ramp_value(q, m.t - 1, m.R);
-    q.to = (double)gain;
-    q.t_set = m.t;
-    q.slope = m.R ? (q.to - q.from) / (double)m.R : 0.0;
+    ramp_set(m.gain, (double)gain, m.clock.t, m.R, true);
     ++m.n_sets;
     return PBSO_OK;
 }
@@ -161,63 +93,48 @@ int Engine::master(const void *d_in, void *d_out) {
     if (!d_in) return fail(PBSO_ERR_INVALID, "master: d_in is NULL");
     Master &m = *master_;
     if (last_nb_ <= 0) return fail(PBSO_ERR_STATE, "master: no step yet");
-    if (tot_steps_ < m.next_step) return fail(PBSO_ERR_STATE, "master: the last step is processed already (or was taken before the master bus was enabled / reset)");
-    if (tot_steps_ > m.next_step)
-        return fail(PBSO_ERR_STATE, "master: a step was not processed, the history is no longer the signal before this step (pbso_master_reset starts over)");
+    if (const int order = m.clock.order(tot_steps_)) return fail(PBSO_ERR_STATE, step_refusal(order, WORDS));
     HIPTRY(hipSetDevice(desc_.device));
     const size_t n = (size_t)last_nb_ * B_, N = (size_t)m.HL + n;
-    float *out = (float *)d_out;
-    if (!out) {
-        GROW(m.out, m.out_cap, (size_t)m.C * n, "master: output");
-        out = m.out;
-    }
-    GROW(m.work, m.work_cap, (size_t)(m.C + 3) * N + n, "master: work arrays");
-    GROW(m.meters, m.meters_cap, (size_t)last_nb_ * m.C, "master: meters");
+    float *out;
+    GROWTRY(m.out.resolve(d_out, (size_t)m.C * n, stream_, out), "master: output: cannot allocate", "master: output");
+    GROWTRY(grow(m.work, (size_t)(m.C + 3) * N + n, stream_), "master: work arrays: cannot allocate", "master: work arrays");
+    GROWTRY(grow(m.meters, (size_t)last_nb_ * m.C, stream_), "master: meters: cannot allocate", "master: meters");
     float *V = m.work, *Rb = V + (size_t)m.C * N, *M0 = Rb + N, *M1 = M0 + N, *G = M1 + N;
-    const int lrc = launch_master((const float *)d_in, m.C, (long long)n, B_, m.hist[m.cur], m.hist[m.cur ^ 1], m.L, m.H, m.T, m.gain, m.R,
-                                  (long long)m.t, m.d_w, V, Rb, M0, M1, G, out, m.meters, stream_);
+    const int lrc = launch_master((const float *)d_in, m.C, (long long)n, B_, m.hist.cur(), m.hist.next(), m.L, m.H, m.T, m.gain, m.R, m.clock.t,
+                                  m.d_w, V, Rb, M0, M1, G, out, m.meters.p, stream_);
     if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_master");
-    m.cur ^= 1;
-    m.t += (int64_t)n;
-    m.next_step = tot_steps_ + 1;
+    m.hist.flip();
+    m.clock.advance((long long)n, tot_steps_);
     ++m.n_calls;
-    m.last_out = out;
-    m.last_nb = last_nb_;
+    m.out.wrote(out, last_nb_);
     return PBSO_OK;
 }
 
-int Engine::read_master(float *out, size_t n) {
-    if (!master_ || !master_->last_out) return fail(PBSO_ERR_STATE, "read_master: no processed step yet");
-    if (!out) return fail(PBSO_ERR_INVALID, "read_master: host_out is NULL");
-    const size_t total = (size_t)master_->C * master_->last_nb * B_;
-    if (n != total) return fail(PBSO_ERR_INVALID, "read_master size mismatch (n = n_channels * n_buffers * frames_per_buffer)");
-    { int src = sync(); if (src != PBSO_OK) return src; }
-    HIPTRY(hipMemcpy(out, master_->last_out, total * sizeof(float), hipMemcpyDeviceToHost));
-    return PBSO_OK;
-}
+int Engine::read_master(float *out, size_t n) { return read_bus(master_ ? &master_->out : nullptr, master_ ? master_->C : 0, WORDS, out, n); }
 
 int Engine::read_master_pcm16(int16_t *out, size_t n) {
-    if (!master_ || !master_->last_out) return fail(PBSO_ERR_STATE, "read_master_pcm16: no processed step yet");
+    if (!master_ || !master_->out.last) return fail(PBSO_ERR_STATE, "read_master_pcm16: no processed step yet");
     if (!out) return fail(PBSO_ERR_INVALID, "read_master_pcm16: host_out is NULL");
     Master &m = *master_;
-    const size_t total = (size_t)m.C * m.last_nb * B_;
+    const size_t total = (size_t)m.C * m.out.last_nb * B_;
     if (n != total) return fail(PBSO_ERR_INVALID, "read_master_pcm16 size mismatch (n = n_channels * n_buffers * frames_per_buffer)");
     HIPTRY(hipSetDevice(desc_.device));
-    GROW(m.pcm, m.pcm_cap, total, "read_master_pcm16: PCM");
-    const int lrc = launch_master_pcm16(m.last_out, m.C, (long long)m.last_nb * B_, (short *)m.pcm, stream_);
+    GROWTRY(grow(m.pcm, total, stream_), "read_master_pcm16: PCM: cannot allocate", "read_master_pcm16: PCM");
+    const int lrc = launch_master_pcm16(m.out.last, m.C, (long long)m.out.last_nb * B_, (short *)m.pcm.p, stream_);
     if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_master_pcm16");
     { int src = sync(); if (src != PBSO_OK) return src; }
-    HIPTRY(hipMemcpy(out, m.pcm, total * sizeof(int16_t), hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out, m.pcm.p, total * sizeof(int16_t), hipMemcpyDeviceToHost));
     return PBSO_OK;
 }
 
 int Engine::read_master_meters(pbso_master_meter *out, size_t n_records) {
-    if (!master_ || !master_->last_out) return fail(PBSO_ERR_STATE, "read_master_meters: no processed step yet");
+    if (!master_ || !master_->out.last) return fail(PBSO_ERR_STATE, "read_master_meters: no processed step yet");
     if (!out) return fail(PBSO_ERR_INVALID, "read_master_meters: out is NULL");
-    const size_t total = (size_t)master_->C * master_->last_nb;
+    const size_t total = (size_t)master_->C * master_->out.last_nb;
     if (n_records != total) return fail(PBSO_ERR_INVALID, "read_master_meters size mismatch (n_records = n_buffers * n_channels)");
     { int src = sync(); if (src != PBSO_OK) return src; }
-    HIPTRY(hipMemcpy(out, master_->meters, total * sizeof(pbso_master_meter), hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out, master_->meters.p, total * sizeof(pbso_master_meter), hipMemcpyDeviceToHost));
     return PBSO_OK;
 }
 
@@ -234,13 +151,9 @@ int Engine::master_reset() {
     if (!master_) return fail(PBSO_ERR_STATE, "master_reset: the master bus is not enabled");
     Master &m = *master_;
     HIPTRY(hipSetDevice(desc_.device));
-    for (float *h : m.hist) HIPTRY(hipMemsetAsync(h, 0, (size_t)m.C * m.HL * sizeof(float), stream_));
-    m.gain.from = m.gain.to;
-    m.gain.t_set = 0;
-    m.gain.slope = 0.0;
-    m.t = 0;
-    m.cur = 0;
-    m.next_step = tot_steps_ + 1;
+    HIPTRY(m.hist.reset(stream_));
+    ramp_settle(m.gain);
+    m.clock.reset(tot_steps_);
     return PBSO_OK;
 }
 
@@ -248,8 +161,8 @@ int Engine::master_info(int64_t out[4]) {
     if (!master_) return fail(PBSO_ERR_STATE, "master_info: the master bus is not enabled");
     if (!out) return fail(PBSO_ERR_INVALID, "master_info: out is NULL");
     const Master &m = *master_;
-    out[0] = m.t;
-    out[1] = m.ramping(m.t) ? m.gain.t_set + m.R - 1 : m.t;
+    out[0] = m.clock.t;
+    out[1] = m.ramping(m.clock.t) ? m.gain.t_set + m.R - 1 : m.clock.t;
     out[2] = m.n_calls;
     out[3] = m.n_sets;
     return PBSO_OK;
