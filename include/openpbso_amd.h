@@ -512,6 +512,34 @@ int pbso_scene_fir_reset(pbso_engine *e);
 /* out[0] = t of the next mixed sample, out[1] = the first t at which the running fade is over (= out[0] when none runs),
  * out[2] = mixes done, out[3] = set calls accepted */
 int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]);
+/* The delay stage of the scene filter mix: a ramped fractional delay per OBJECT in front of the filters -- a moving source heard
+ * through head-related filters; its changing time of flight is a Doppler shift instead of a cross-fade between two onsets.
+ *     y_c(t; h, D) = sum_o sum_k h_co[k] * z_o(t - D_o - k)
+ * is the text above with z_o in place of x_o: the chain order, the groups of 32 and the cross-fade's blend are the same, both
+ * filter sets of a cross-fade read the same z, and the integer onset stays and adds to the delay.  z_o(tau) is 0 for tau < 0.
+ * The delay d_o is an f32 value kept as fp64 and ramped over R_d = ramp_samples by exactly the scene mix's rule and order of
+ * arithmetic (p(t) = from + slope * (t - t_set + 1) in fp64, slope divided once when the set takes effect, p(t) = to from
+ * t_set + R_d - 1 on): a set takes effect at t_set = the first sample of the next mixed step; a set during a ramp starts from
+ * p(t_set - 1); the first set after the delay stage is enabled or the mixer reset takes effect without a ramp; until then every
+ * delay is 0.  A set that follows another with no mix in between replaces it.  For tau >= 0, with the record in force at tau:
+ *     d  = p_o(tau)                                                        (fp64)
+ *     fr = d - floor(d);   i0 = tau - (long)floor(d) - (fr != 0);   f = fr != 0 ? (float)(1.0 - fr) : 0.f
+ *     z_o(tau) = f == 0.f ? x_o(i0) : x_o(i0) + f * (x_o(i0 + 1) - x_o(i0))     three rounded f32 operations, none fused
+ * -- the scene mix's read, word for word; i0 + 1 <= tau always: nothing reads the future.  Past values stay fixed: z_o(tau) is defined by the record in force at
+ * tau, never by a later one extrapolated backwards.  The device therefore keeps two histories per object, the last max_delay + 1
+ * samples of x (what z of the next step reads) and the last max_onset + K - 1 samples of z (what the filters' window of the next
+ * step reads); z itself is computed on the way into the filters and never stored as rows.  So the output stays bit-reproducible
+ * and depends on the rows, the sets and the absolute samples at which they took effect only, not on the cut into steps;
+ * tests/cpp/scene_fir_delay_ref.c states z as plain C.
+ * pbso_scene_fir_delay_enable needs pbso_scene_fir_enable first and a mixer that has mixed nothing since its enable or its last
+ * reset (else PBSO_ERR_STATE); a new pbso_scene_fir_enable drops the delay stage with everything else; pbso_scene_fir_reset
+ * clears both histories and keeps the delays last set, their ramps finished.  A delay set is independent of the filter sets'
+ * cross-fade: it is accepted while a fade runs.  A mixer without the delay stage behaves, and is launched, as before.        */
+int pbso_scene_fir_delay_enable(pbso_engine *e, int max_delay, int ramp_samples);   /* both 0 .. 1 << 20 */
+int pbso_scene_fir_set_delay(pbso_engine *e, const float *delay);   /* [n_objects], finite, 0 <= d <= max_delay; PBSO_ERR_STATE without the enable */
+/* out[0] = max_delay, out[1] = ramp_samples, out[2] = the first t at which every delay ramp is over (= the next mixed t when none
+ * runs), out[3] = delay sets accepted */
+int pbso_scene_fir_delay_info(pbso_engine *e, int64_t out[4]);
 
 /* Scene reverb: a bus effect behind the mixers -- n_in device-resident signals (a send bus: what pbso_mix_objects, pbso_scene_mix
  * or pbso_scene_fir just wrote, or some of their channels) convolved with a long impulse response per (output channel, input),
@@ -683,6 +711,12 @@ int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *dela
  * global id.  After pbso_group_finalize; the arguments as for a single engine.                                              */
 int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int max_onset, int xfade_samples);
 int pbso_group_scene_fir_set(pbso_group *g, const float *taps, const int *onset);
+/* ... and its delay stage on every local rank; delay [n_objects of the whole job] by global object id, sliced per rank.  Checked
+ * for the whole job before any rank takes it.  The enable goes rank by rank, as every enable of the group does: should a rank fail
+ * (PBSO_ERR_NOMEM), the ranks before it have the stage and the group does not count it as enabled; pbso_group_scene_fir_enable
+ * again, which drops the stage on every rank, puts the group back in one state. */
+int pbso_group_scene_fir_delay_enable(pbso_group *g, int max_delay, int ramp_samples);
+int pbso_group_scene_fir_set_delay(pbso_group *g, const float *delay);
 /* the last gather's result on a local rank, a device pointer: ALL -> [world_size * rows_per_rank][n_buffers * 513] (rank r's
  * objects from row r * rows_per_rank; shards smaller than the largest are padded with silent rows), ROOT -> the same on rank 0
  * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE and FIR -> [C][n_buffers * 513].  rows / row_floats (may be NULL)

@@ -33,6 +33,9 @@ EXPORTS = [
     # the scene filter mix (C channels, K taps per channel and object behind an onset per object)
     "pbso_scene_fir_enable", "pbso_scene_fir_set", "pbso_scene_fir", "pbso_read_scene_fir", "pbso_scene_fir_reset", "pbso_scene_fir_info",
     "pbso_group_scene_fir_enable", "pbso_group_scene_fir_set",
+    # ... and its delay stage (a ramped fractional delay per object in front of the filters)
+    "pbso_scene_fir_delay_enable", "pbso_scene_fir_set_delay", "pbso_scene_fir_delay_info",
+    "pbso_group_scene_fir_delay_enable", "pbso_group_scene_fir_set_delay",
     # the scene reverb (n_in bus signals through K taps, up to 1 << 17, per output channel and input)
     "pbso_scene_reverb_enable", "pbso_scene_reverb_set", "pbso_scene_reverb", "pbso_read_scene_reverb", "pbso_scene_reverb_reset",
     "pbso_scene_reverb_info",
@@ -216,6 +219,12 @@ def lib():
         l.pbso_scene_fir_info.argtypes = [vp, C.POINTER(C.c_int64)]
         l.pbso_group_scene_fir_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         l.pbso_group_scene_fir_set.argtypes = [vp, fp, ip]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_fir_delay_enable"):
+        l.pbso_scene_fir_delay_enable.argtypes = [vp, C.c_int, C.c_int]
+        l.pbso_scene_fir_set_delay.argtypes = [vp, fp]
+        l.pbso_scene_fir_delay_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_group_scene_fir_delay_enable.argtypes = [vp, C.c_int, C.c_int]
+        l.pbso_group_scene_fir_set_delay.argtypes = [vp, fp]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_reverb"):
         l.pbso_scene_reverb_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         l.pbso_scene_reverb_set.argtypes = [vp, fp]

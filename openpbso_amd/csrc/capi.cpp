@@ -532,6 +532,28 @@ int pbso_scene_fir_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_scene_fir_delay_enable(pbso_engine *e, int max_delay, int ramp_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_fir_delay_enable(max_delay, ramp_samples);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_set_delay(pbso_engine *e, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_set_delay(delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_delay_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_delay_info(out);
+    GUARD_END(e)
+}
+
 int pbso_scene_reverb_enable(pbso_engine *e, int n_in, int n_out, int n_taps, int xfade_samples) {
     NEED(e);
     GUARD_BEGIN

@@ -259,6 +259,10 @@ public:
     int read_scene_fir(float *out, size_t n);
     int scene_fir_reset();
     int scene_fir_info(int64_t out[4]);
+    // ... behind a ramped fractional delay per object (kernels_fir_delay.hip)
+    int scene_fir_delay_enable(int max_delay, int ramp_samples);
+    int scene_fir_set_delay(const float *delay);
+    int scene_fir_delay_info(int64_t out[4]);
     // the scene reverb (scene_reverb.cpp, kernels_reverb.hip): a caller's n_in bus signals through K taps per (output channel, input)
     int scene_reverb_enable(int n_in, int n_out, int n_taps, int xfade_samples);
     int scene_reverb_set(const float *taps);

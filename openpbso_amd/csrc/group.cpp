@@ -103,6 +103,8 @@ struct pbso_group {
     int scene_c = 0, scene_max_delay = 0;                // the scene mixer (pbso_group_scene_mix_enable)
     bool scene_on = false, scene_mixed = false;          // ... and whether the last step has had its PBSO_GATHER_SCENE
     int fir_c = 0, fir_k = 0, fir_max_onset = 0;         // the scene filter mix (pbso_group_scene_fir_enable)
+    int fir_max_delay = 0;                               // ... its delay stage (pbso_group_scene_fir_delay_enable)
+    bool fir_delay_on = false;
     bool fir_on = false, fir_mixed = false;              // ... and whether the last step has had its PBSO_GATHER_FIR
     bool use_rccl = false;                               // a communicator exists: the collectives go through librccl
     bool loopback() const { return transport == PBSO_GROUP_LOOPBACK; }
@@ -538,6 +540,7 @@ int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int m
     g->fir_c = n_channels;
     g->fir_k = n_taps;
     g->fir_max_onset = max_onset;
+    g->fir_delay_on = false;                             // (a new enable drops the delay stage with everything else)
     g->fir_mixed = true;                                 // (armed for the next step, as every engine is)
     return PBSO_OK;
 }
@@ -565,6 +568,29 @@ int pbso_group_scene_fir_set(pbso_group *g, const float *taps, const int *onset)
     } catch (const std::exception &ex) {
         return gfail(g, PBSO_ERR_NOMEM, ex.what());
     }
+    return PBSO_OK;
+}
+
+int pbso_group_scene_fir_delay_enable(pbso_group *g, int max_delay, int ramp_samples) {
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, "scene_fir_delay_enable: the group's scene filter mix is not enabled");
+    if (max_delay < 0 || max_delay > (1 << 20) || ramp_samples < 0 || ramp_samples > (1 << 20))
+        return gfail(g, PBSO_ERR_INVALID, "scene_fir_delay_enable: max_delay and ramp_samples 0 .. 1 << 20");
+    for (Rank &rk : g->ranks)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_fir_delay_enable(rk.eng, max_delay, ramp_samples));
+    g->fir_delay_on = true;
+    g->fir_max_delay = max_delay;
+    return PBSO_OK;
+}
+
+int pbso_group_scene_fir_set_delay(pbso_group *g, const float *delay) {
+    if (!g || !g->fir_on || !g->fir_delay_on) return gfail(g, PBSO_ERR_STATE, "scene_fir_set_delay: the group's delay stage is not enabled");
+    if (!delay) return gfail(g, PBSO_ERR_INVALID, "scene_fir_set_delay: delay is NULL");
+    // checked for the whole job first: no rank takes a set that another one refuses
+    for (size_t o = 0; o < (size_t)g->n_objects; ++o)
+        if (!(std::isfinite(delay[o]) && delay[o] >= 0.f && delay[o] <= (float)g->fir_max_delay))
+            return gfail(g, PBSO_ERR_INVALID, "scene_fir_set_delay: a delay is not finite or outside [0, max_delay]");
+    for (Rank &rk : g->ranks)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_fir_set_delay(rk.eng, delay + g->cuts[rk.rank]));
     return PBSO_OK;
 }
 

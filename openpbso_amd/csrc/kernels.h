@@ -373,6 +373,14 @@ int launch_scene_fir_prepare(const float *taps, long long n_co, int K, float *P,
 int launch_scene_fir(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const float *P_to,
                      const float *P_from, const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0,
                      long long t_set, int R, float *parts, float *out, hipStream_t stream);
+// pbso_scene_fir behind pbso_scene_fir_delay_enable (kernels_fir_delay.hip): the same with z_o in place of x_o, z_o(t0 + j) = the
+// scene mix's read of hist_x ++ rows at t0 + j - d_o(t0 + j), d_o = ramp_value(params[o], ., Rd); params [n_obj].  hist_z [n_obj][H]
+// the H samples of z before the step, hist_x [n_obj][Hx] the Hx = max_delay + 1 samples of x before it.  Then hist_z_next = the
+// last H samples of hist_z ++ z(step) and hist_x_next = the last Hx samples of hist_x ++ rows.
+int launch_scene_fir_delay(const float *rows, int n_obj, long long n, const float *hist_z, float *hist_z_next, int H, const float *hist_x,
+                           float *hist_x_next, int Hx, const SceneParam *params, int Rd, const float *P_to, const float *P_from,
+                           const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0, long long t_set, int R,
+                           float *parts, float *out, hipStream_t stream);
 
 // pbso_scene_reverb (kernels_reverb.hip): n_in bus signals convolved with K f32 taps per (output channel, input), the taps cut into
 // segments of SCENE_REVERB_SEGMENT: one fmaf chain per (channel, input, segment, sample) on the f32 MFMA, the segments' rows then

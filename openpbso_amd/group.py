@@ -160,6 +160,16 @@ class Group:
         self._chk(self._l.pbso_group_scene_fir_set(self._h, h.ctypes.data_as(C.POINTER(C.c_float)),
                                                    None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
 
+    def scene_fir_delay_enable(self, max_delay, ramp_samples=0):
+        """pbso_group_scene_fir_delay_enable: the filter mix's delay stage on every local rank"""
+        self._chk(self._l.pbso_group_scene_fir_delay_enable(self._h, max_delay, ramp_samples))
+
+    def scene_fir_set_delay(self, delay):
+        """pbso_group_scene_fir_set_delay: delay [n_objects of the job] in samples, by global id"""
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == len(self._modes)
+        self._chk(self._l.pbso_group_scene_fir_set_delay(self._h, d.ctypes.data_as(C.POINTER(C.c_float))))
+
     def sync(self):
         self._chk(self._l.pbso_group_sync(self._h))
 

@@ -622,6 +622,22 @@ class Engine:
         self._chk(self._l.pbso_scene_fir_info(self._h, v))
         return {"t": v[0], "fade_end": v[1], "mixes": v[2], "sets": v[3]}
 
+    def scene_fir_delay_enable(self, max_delay, ramp_samples=0):
+        """pbso_scene_fir_delay_enable: a ramped fractional delay per object in front of the filters (before the first mix)"""
+        self._chk(self._l.pbso_scene_fir_delay_enable(self._h, max_delay, ramp_samples))
+
+    def scene_fir_set_delay(self, delay):
+        """pbso_scene_fir_set_delay: delay [n_objects] in samples, 0 <= d <= max_delay"""
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == len(self.n_modes)
+        self._chk(self._l.pbso_scene_fir_set_delay(self._h, d.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_delay_info(self):
+        """pbso_scene_fir_delay_info: max_delay, ramp_samples, the first t at which every delay ramp is over, delay sets"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_fir_delay_info(self._h, v))
+        return {"max_delay": v[0], "ramp_samples": v[1], "ramp_end": v[2], "sets": v[3]}
+
     # -- scene reverb: n_in device-resident bus signals through K taps per (output channel, input), history kept across steps ----
     def scene_reverb_enable(self, n_in, n_out, n_taps, xfade_samples=0):
         """pbso_scene_reverb_enable: from the next step on, every step is processed exactly once (scene_reverb)"""

@@ -36,6 +36,10 @@
 //                    buffer on, cross-faded over N samples (default 441; change points must be at least that far apart).  A taps
 //                    file is raw little-endian float32 [C][K], every file with the same K; every distinct path is loaded once.
 //                    Not together with --pan.
+//   --fir-delay FILE [--delay-ramp N]    with --fir: the filter mix's delay stage (pbso_scene_fir_delay_enable): lines <buffer> <copy>
+//                    <delay in samples> set copy's fractional delay in front of its filters from that buffer on, ramped over N
+//                    samples (default 441; a moving source's Doppler shift).  max_delay is the file's largest value, rounded
+//                    up; the run is cut at these lines' buffers too.
 //   --reverb FILE [--reverb-xfade N]     with --channels C and one of --pan / --fir: the room behind the mix (pbso_scene_reverb).  The
 //                    file is an impulse response per output channel, raw little-endian float32 [C][K], K = file size / 4 C up to
 //                    131072; the send bus is the object mix (pbso_mix_objects, one input), and the WAV is dry + wet: every
@@ -198,6 +202,7 @@ static void feed_strokes(pbso_engine *e, const StrokeScript &sc, const std::vect
 // --channels / --pan: the scene mix's script
 struct Pan { long b; int copy; std::vector<float> gd; };   // gd: g_0 d_0 ... g_{C-1} d_{C-1}
 struct FirLine { long b; int copy, onset, file; };          // file: index into Scene::fir_files
+struct FirDelayLine { long b; int copy; float delay; };     // --fir-delay: <buffer> <copy> <delay in samples>
 struct Scene {
     int channels = 0, ramp = 441, copies = 1, max_delay = 0;
     std::vector<Pan> lines;
@@ -206,6 +211,9 @@ struct Scene {
     int xfade = 441, n_taps = 0, max_onset = 0;
     std::vector<FirLine> fir_lines;
     std::vector<std::vector<float>> fir_files;           // [C][K] each
+    // --fir-delay: the filter mix's delay stage (a ramped fractional delay per copy in front of the filters)
+    std::vector<FirDelayLine> fir_delay_lines;
+    int fir_max_delay = 0, fir_delay_ramp = 441;
     // --reverb: an impulse response [C][reverb_taps] behind either mixer
     std::vector<float> reverb;
     int reverb_taps = 0, reverb_xfade = 441;
@@ -215,6 +223,8 @@ struct Scene {
         for (const Pan &p : lines)
             if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         for (const FirLine &p : fir_lines)
+            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+        for (const FirDelayLine &p : fir_delay_lines)
             if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         std::sort(c.begin(), c.end());
         c.erase(std::unique(c.begin(), c.end()), c.end());
@@ -241,6 +251,16 @@ struct Scene {
                     std::copy(fir_files[p.file].begin() + (size_t)c * n_taps, fir_files[p.file].begin() + (size_t)(c + 1) * n_taps,
                               taps.begin() + ((size_t)c * copies + p.copy) * n_taps);
                 onset[p.copy] = p.onset;
+                any = true;
+            }
+        return any;
+    }
+    // ... and delay [copies]
+    bool fir_delay_set_at(long b, std::vector<float> &delay) const {
+        bool any = false;
+        for (const FirDelayLine &p : fir_delay_lines)
+            if (p.b == b) {
+                delay[p.copy] = p.delay;
                 any = true;
             }
         return any;
@@ -334,6 +354,9 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
         if (scene->fir) gcheck(g, pbso_group_scene_fir_enable(g, C, scene->n_taps, scene->max_onset, scene->xfade), "group_scene_fir_enable");
         else gcheck(g, pbso_group_scene_mix_enable(g, C, scene->max_delay, scene->ramp), "group_scene_mix_enable");
+        if (!scene->fir_delay_lines.empty())
+            gcheck(g, pbso_group_scene_fir_delay_enable(g, scene->fir_max_delay, scene->fir_delay_ramp), "group_scene_fir_delay_enable");
+        std::vector<float> fir_delay(copies, 0.f);
         std::vector<float> gain((size_t)C * copies, 0.f), delay((size_t)C * copies, 0.f), seg;
         std::vector<float> taps(scene->fir ? (size_t)C * copies * scene->n_taps : 0, 0.f);
         std::vector<int> onset(copies, 0);
@@ -342,6 +365,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
             if (scene->fir) {
                 if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
+                if (scene->fir_delay_set_at(cuts[k], fir_delay)) gcheck(g, pbso_group_scene_fir_set_delay(g, fir_delay.data()), "group_scene_fir_set_delay");
             } else if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
             const int nb = cuts[k + 1] - cuts[k];
             const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
@@ -373,7 +397,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, reverb, strokes_file, arprm_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_delay, reverb, strokes_file, arprm_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
@@ -410,7 +434,9 @@ int main(int argc, char **argv) {
         else if (a == "--pan") pan = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else if (a == "--fir") fir = val();
+        else if (a == "--fir-delay") fir_delay = val();
         else if (a == "--xfade") scene.xfade = std::atoi(val().c_str());
+        else if (a == "--delay-ramp") scene.fir_delay_ramp = std::atoi(val().c_str());
         else if (a == "--reverb") reverb = val();
         else if (a == "--reverb-xfade") scene.reverb_xfade = std::atoi(val().c_str());
         else if (a == "--limit") { limit = true; limit_T = (float)std::atof(val().c_str()); }
@@ -601,6 +627,7 @@ int main(int argc, char **argv) {
     }
     const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
     if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
+    if (!fir_delay.empty() && fir.empty()) die("--fir-delay needs --fir FILE: the delay sits in front of the filter mix");
     if (mixed && (scene.channels < 1 || scene.channels > 8)) die("--channels must be 1 .. 8");
     if (!fir.empty()) {
         // the scene filter mix's script: <buffer> <copy> <onset> <taps file>
@@ -641,6 +668,24 @@ int main(int argc, char **argv) {
             scene.fir_lines.push_back(p);
         }
         if (scene.fir_lines.empty()) die("no lines in " + fir);
+        if (!fir_delay.empty()) {
+            // the delay stage's script: <buffer> <copy> <delay in samples>; max_delay is the largest value, rounded up
+            if (scene.fir_delay_ramp < 0 || scene.fir_delay_ramp > (1 << 20)) die("--delay-ramp must be 0 .. 1048576");
+            std::ifstream df(fir_delay);
+            if (!df) die("cannot read " + fir_delay);
+            while (std::getline(df, line)) {
+                if (line.empty() || line[0] == '#') continue;
+                std::istringstream iss(line);
+                FirDelayLine p;
+                if (!(iss >> p.b >> p.copy >> p.delay)) die("bad fir-delay line (<buffer> <copy> <delay in samples>): " + line);
+                if (p.copy < 0 || p.copy >= scene.copies) die("fir-delay line for a copy that does not exist: " + line);
+                if (p.b < 0 || p.b >= n_buffers) die("fir-delay line outside buffers 0 .. --buffers - 1: " + line);
+                if (!(p.delay >= 0.f && p.delay <= (float)(1 << 20))) die("fir delay outside [0, 1048576]: " + line);
+                scene.fir_max_delay = std::max(scene.fir_max_delay, (int)std::ceil(p.delay));
+                scene.fir_delay_lines.push_back(p);
+            }
+            if (scene.fir_delay_lines.empty()) die("no lines in " + fir_delay);
+        }
     } else if (mixed) {
         // the scene mix's script: <buffer> <copy> then a gain and a delay per channel
         if (pan.empty()) die("--channels needs --pan FILE or --fir FILE");
@@ -741,6 +786,9 @@ int main(int argc, char **argv) {
             const size_t total = (size_t)n_run * PBSO_FRAMES_PER_BUFFER;
             if (scene.fir) check(e, pbso_scene_fir_enable(e, C, scene.n_taps, scene.max_onset, scene.xfade), "scene_fir_enable");
             else check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
+            if (!scene.fir_delay_lines.empty())
+                check(e, pbso_scene_fir_delay_enable(e, scene.fir_max_delay, scene.fir_delay_ramp), "scene_fir_delay_enable");
+            std::vector<float> delay_now(1, 0.f);
             std::vector<float> gain(C, 0.f), delay(C, 0.f), seg;
             std::vector<float> taps(scene.fir ? (size_t)C * scene.n_taps : 0, 0.f);
             std::vector<int> onset(1, 0);
@@ -761,6 +809,7 @@ int main(int argc, char **argv) {
                     // (--limit's tail: the script ended with the run)
                 } else if (scene.fir) {
                     if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
+                    if (scene.fir_delay_set_at(cuts[k], delay_now)) check(e, pbso_scene_fir_set_delay(e, delay_now.data()), "scene_fir_set_delay");
                 } else if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
                 const int nb = cuts[k + 1] - cuts[k];
                 const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
