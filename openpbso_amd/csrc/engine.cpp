@@ -139,6 +139,23 @@ void PinBuf<T>::release() {
     cap = 0;
 }
 
+// every element type the engine's files use (the definitions above are in this file only)
+template struct DevBuf<float>;
+template struct DevBuf<double>;
+template struct DevBuf<int>;
+template struct DevBuf<unsigned>;
+template struct DevBuf<long long>;
+template struct DevBuf<unsigned long long>;
+template struct DevBuf<unsigned char>;
+template struct DevBuf<TeamDesc>;
+template struct DevBuf<SplitObj>;
+template struct DevBuf<FfatGeom>;
+template struct DevBuf<FfatShared>;
+template struct DevBuf<ArState>;
+template struct DevBuf<ArRec>;
+template struct DevBuf<ArFin>;
+template struct PinBuf<unsigned char>;
+
 void Engine::PlanSet::release() {
     h_arena.release(); d_arena.release(); d_tprof.release();
 }
@@ -335,34 +352,6 @@ int Engine::hip_fail(hipError_t e, const char *what) {
     err_ = std::string(what) + ": " + hipGetErrorString(e);
     return PBSO_ERR_HIP;
 }
-#define LAUNCHTRY(expr)                                                \
-    do {                                                               \
-        int _e = (expr);                                               \
-        if (_e != 0) return hip_fail((hipError_t)_e, #expr);           \
-    } while (0)
-// Engine::step_chunk's stream calls: made at once, or -- with the second submitting thread (submit_queue.h) -- recorded with their
-// arguments evaluated HERE and made by the worker.  `defer` and `ops` are step_chunk's locals.
-#define QHIP(fn, ...)                                                                      \
-    do {                                                                                   \
-        if (defer) ops.push_back(make_submit_op(#fn, fn, __VA_ARGS__));                    \
-        else HIPTRY(fn(__VA_ARGS__));                                                      \
-    } while (0)
-#define QLAUNCH(fn, ...)                                                                   \
-    do {                                                                                   \
-        if (defer) ops.push_back(make_submit_op(#fn, fn, __VA_ARGS__));                    \
-        else LAUNCHTRY(fn(__VA_ARGS__));                                                   \
-    } while (0)
-// a device buffer that has to GROW while recorded calls are still waiting: its keep-copy and the retirement of the old block are
-// immediate calls and must come behind them in their streams -- wait for the worker first (rare: the first steps of an engine)
-#define GROWTRY(buf, n, keep, s)                                                           \
-    do {                                                                                   \
-        if (defer && (size_t)(n) > (buf).cap) {                                            \
-            int _d = drain_submit();                                                       \
-            if (_d != PBSO_OK) return _d;                                                  \
-        }                                                                                  \
-        HIPTRY((buf).ensure((n), (keep), (s)));                                            \
-    } while (0)
-
 int Engine::init() {
     if (desc_.abi_version != PBSO_ABI_VERSION) return fail(PBSO_ERR_INVALID, "abi_version mismatch");
     if (desc_.frames_per_buffer > 0) B_ = desc_.frames_per_buffer;
@@ -501,732 +490,6 @@ int Engine::init() {
     tc_mode_ = desc_.time_chunks;
     tc_shape_ = desc_.time_chunk_shape;
     if (desc_.scan_kernel < 0 || desc_.scan_kernel > 2) return fail(PBSO_ERR_INVALID, "scan_kernel");
-    return PBSO_OK;
-}
-
-// BuildSolver -> ModalIntegrator<double>::Build + ctor, modal_integrator.h:47-101
-int Engine::add_object(const pbso_object_desc &d, int *id) {
-    if (finalized_) return fail(PBSO_ERR_STATE, "add_object after finalize");
-    if (d.n_modes < 0 || d.n_omega < d.n_modes || (d.n_modes > 0 && !d.omega_squared))
-        return fail(PBSO_ERR_INVALID, "N for modal integrator invalid");         // assert :56
-    Object o;
-    o.n_modes = d.n_modes;
-    o.c1.resize(d.n_modes);
-    o.c2.resize(d.n_modes);
-    o.c3.resize(d.n_modes);
-    const double h = 1.0 / (double)rate_;
-    for (int ii = 0; ii < d.n_modes; ++ii) {
-        const double omega0 = std::sqrt(d.omega_squared[ii] / d.density);         // :63
-        const double xi = 0.5 * (d.alpha / omega0 + d.beta * omega0);             // :64
-        const double a = 2.0 * xi * omega0;                                       // :65
-        const double b = std::pow(omega0, 2);                                     // :66
-        const double epsilon = std::exp(-a / 2 * h);                              // :89
-        const double theta = h * std::sqrt(b - a * a / 4.0);                      // :90
-        const double gamma = std::asin(a / (2.0 * std::sqrt(b)));                 // :91
-        const double omega = std::sqrt(b);                                        // :92
-        const double omega_d = std::sqrt(b - std::pow(a, 2) / 4.0);               // :93
-        o.c1[ii] = 2.0 * epsilon * std::cos(theta);                               // :95
-        o.c2[ii] = -std::pow(epsilon, 2);                                         // :96
-        double c3 = 2.0 * (epsilon * std::cos(theta + gamma)
-                           - std::pow(epsilon, 2) * std::cos(2.0 * theta + gamma));  // :97
-        c3 /= (3.0 * omega * omega_d);                                            // :98
-        c3 *= 1E9;                                                                // :99
-        o.c3[ii] = c3;
-    }
-    if (d.mode_shapes && d.n_dof > 0) {
-        o.n_dof = d.n_dof;
-        o.shapes.assign(d.mode_shapes, d.mode_shapes + (size_t)d.n_modes * d.n_dof);
-    }
-    objs_.push_back(std::move(o));
-    if (id) *id = (int)objs_.size() - 1;
-    return PBSO_OK;
-}
-
-// ModalSolver::readFFATMaps, modal_solver.h:278-284 (std::map keyed by modeId)
-int Engine::set_ffat_maps(int obj, const pbso_ffat_map *maps, int n) {
-    if (finalized_) return fail(PBSO_ERR_STATE, "set_ffat_maps after finalize");
-    if (!valid_obj(obj) || n < 0 || (n > 0 && !maps)) return fail(PBSO_ERR_INVALID, "set_ffat_maps arguments");
-    Object &o = objs_[obj];
-    o.have_maps = true;               // LoadAll returns a non-null (possibly empty) map, SURVEY Q12
-    o.geom.clear();
-    o.psi.clear();
-    o.n_maps = 0;
-    for (int i = 0; i < n; ++i) {
-        const pbso_ffat_map &m = maps[i];
-        if (m.mode_id < 0) return fail(PBSO_ERR_INVALID, "negative modeId");
-        if ((int)o.geom.size() <= m.mode_id) {
-            FfatGeom z;
-            std::memset(&z, 0, sizeof(z));
-            o.geom.resize(m.mode_id + 1, z);
-        }
-        FfatGeom &g = o.geom[m.mode_id];
-        if (!g.valid) o.n_maps++;
-        // every index GetMapVal can form must be inside psi
-        for (int f = 0; f < 6; ++f) {
-            if (m.n_elements[f][0] < 1 || m.n_elements[f][1] < 1 || m.strides[f] < 0 ||
-                (long long)m.strides[f] + (long long)m.n_elements[f][0] * m.n_elements[f][1] > m.n_psi)
-                return fail(PBSO_ERR_INVALID, "FFAT map strides/n_elements exceed psi");
-        }
-        g.k = m.k;
-        g.cell_size = m.cell_size;
-        for (int j = 0; j < 3; ++j) {
-            g.center3[j] = m.center3[j];
-            g.center[j] = m.center[j];
-            g.bbox_low[j] = m.bbox_low[j];
-            g.bbox_top[j] = m.bbox_top[j];
-        }
-        for (int f = 0; f < 6; ++f) {
-            for (int j = 0; j < 3; ++j) g.low_corners[f][j] = m.low_corners[f][j];
-            g.n_elements[f][0] = m.n_elements[f][0];
-            g.n_elements[f][1] = m.n_elements[f][1];
-            g.strides[f] = m.strides[f];
-        }
-        g.n_psi = m.n_psi;
-        g.valid = 1;
-        g.psi_off = (long long)o.psi.size();       // a replaced map leaves its old psi unused
-        o.psi.insert(o.psi.end(), m.psi, m.psi + m.n_psi);
-    }
-    return PBSO_OK;
-}
-
-// Closed-form qnorm matrices (getQBufferNorm, modal_solver.h:270-273): G = sum_{k=0}^{B-1} (A^k)' e1 e1' A^k per mode,
-// in fp64, in the basis x = (q_k, q_k - q_{k-1}) (well conditioned at low frequency; the direct-form kernel forms the
-// difference itself): A = [[1-e, eps^2], [-e, eps^2]], e = 1 - c1 - c2, eps^2 = -c2.  Row r_k = e1' A^k: r_{k+1} = r_k A.
-// Built by finalize() for the engines that report qnorm rows in closed form, and by listeners_enable() for a block
-// engine created with PBSO_QNORM_OFF (the build of the bank that keeps block-start states always evaluates the rows).
-int Engine::build_gq() {
-    if (d_gq_.p) return PBSO_OK;
-    const int N = (int)objs_.size();
-    const size_t nm = (size_t)N * m_pad_;
-    std::vector<float> gq(3 * nm, 0.f);
-    for (int i = 0; i < N; ++i) {
-        const Object &o = objs_[i];
-        for (int m = 0; m < o.n_modes; ++m) {
-            const double eps2 = -o.c2[m], e = (1.0 - o.c1[m]) - o.c2[m];
-            const double a00 = 1.0 - e, a01 = eps2, a10 = -e, a11 = eps2;
-            double r0 = 1.0, r1 = 0.0, s11 = 0.0, s12 = 0.0, s22 = 0.0;
-            for (int k = 0; k < B_; ++k) {
-                s11 += r0 * r0; s12 += r0 * r1; s22 += r1 * r1;
-                const double n0 = r0 * a00 + r1 * a10, n1 = r0 * a01 + r1 * a11;
-                r0 = n0; r1 = n1;
-            }
-            const size_t k = (size_t)i * m_pad_ + m;
-            gq[k] = (float)s11;
-            gq[nm + k] = (float)(2.0 * s12);
-            gq[2 * nm + k] = (float)s22;
-        }
-    }
-    HIPTRY(d_gq_.ensure(3 * nm));
-    HIPTRY(hipMemcpy(d_gq_.p, gq.data(), 3 * nm * sizeof(float), hipMemcpyHostToDevice));
-    return PBSO_OK;
-}
-
-int Engine::finalize() {
-    HIPTRY(hipSetDevice(desc_.device));      // the caller's thread may have another device current
-    if (finalized_) return fail(PBSO_ERR_STATE, "finalize called twice");
-    if (objs_.empty()) return fail(PBSO_ERR_STATE, "no objects");
-    const int N = (int)objs_.size();
-    {
-        // The second preparation stream (round 5, step_chunk's fork), for engines large enough for the fork to matter.  Created
-        // HERE, not with the engine and not at the first fork: every stream a process owns shifts which hardware queue the next
-        // one lands on -- created with every engine it doubled the cross-stream hand-over of one-buffer steps of small engines
-        // (58 -> 112 us, scripts/latency.py, latency_path = -1: any third stream does, whatever its priority class), created at
-        // the first fork it came to share a queue with the bank (8 x 4096 x 86 scraping: 0.30 -> 0.40 ms per step;
-        // scripts/debug/r05_aux_queue.sh).  Large OBJECTS: that is where projection and combine are long enough to be worth a
-        // stream (64 x 256 with a moving listener, host-bound, 0.13 - 0.15 ms per step without the third stream and 0.15 - 0.19
-        // with it).  PBSO_PREP_SPLIT=2 creates it for any engine (tests), 0 never.
-        long long modes = 0;
-        for (const Object &o : objs_) modes += o.n_modes;
-        if (prep_split_ == 2 || (prep_split_ == 1 && modes >= 32768 && modes >= 1024LL * N))
-            HIPTRY(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, prep_priority_));
-    }
-    // Team shape: R oscillators per lane; an object of n modes needs ceil(n / 64R) waves, cut into
-    // teams (workgroups) of at most MAX_WAVES_PER_TEAM waves.  The VALU issue rate needs ~4 waves per
-    // SIMD (4096 on the chip, profiles/r01_microbench.txt).
-    int R = desc_.modes_per_lane;
-    if (R != 0 && R != 1 && R != 2 && R != 3 && R != 4 && R != 8) return fail(PBSO_ERR_INVALID, "modes_per_lane must be 0,1,2,3,4,8");
-    const bool block = is_block();
-    // (round 6: the block form's eight-modes-per-lane builds -- one wave per SIMD, 300 - 460 bytes of scratch per lane -- were never a
-    //  policy's choice and are gone)
-    if (block && (R == 3 || R == 8)) return fail(PBSO_ERR_INVALID, "modes_per_lane must be 0,1,2,4 in the block form");
-
-    auto waves_of = [&](const Object &o, int r) { return std::max(1, (o.n_modes + 64 * r - 1) / (64 * r)); };
-    auto total_waves = [&](int r) {
-        long long w = 0;
-        for (const Object &o : objs_) w += waves_of(o, r);
-        return w;
-    };
-    if (R == 0 && block) {
-        // The block form is paced by the matrix pipe: two waves per SIMD keep it busy (one issues MFMAs while
-        // the other steps its coarse recurrence), and a wave holds 32 R operand registers for its W table.
-        // The fewest modes per lane that fit the chip at two waves per SIMD; more objects run in rounds.
-        R = 4;
-        for (int r : {1, 2, 4})
-            if (total_waves(r) <= 8LL * n_cus_) { R = r; break; }
-    }
-    if (R == 0) {
-        // the fewest modes per lane whose waves are all resident at once (16 waves per CU is what the
-        // LDS tiles allow: 4096 on the chip) -- a second round of workgroups costs more than the
-        // deeper per-lane work (768 x 512: 2.83 ms with R = 1 in two rounds, 1.93 ms with R = 2).
-        // Engines that cannot be resident at once with R <= 4 minimise rounds x instructions per
-        // wave-sample (5 R + 2.2); R = 8 needs more registers than 4 waves per SIMD leave.
-        R = 0;
-        for (int r : {1, 2, 3, 4})
-            if (total_waves(r) <= 16LL * n_cus_) { R = r; break; }
-        if (R == 0) {
-            double best = 0;
-            for (int r : {1, 2, 3, 4}) {
-                const double cost = (double)((total_waves(r) + 16LL * n_cus_ - 1) / (16LL * n_cus_)) * (5.0 * r + 2.2);
-                if (R == 0 || cost < best) { R = r; best = cost; }
-            }
-        }
-    }
-    int wmax = 1;
-    for (const Object &o : objs_) wmax = std::max(wmax, waves_of(o, R));
-    R_ = R;
-    m_pad_ = 64 * R * wmax;
-    // K5 (kernels_scan.hip): launches cut along the time axis pick their team shape per launch, up to four modes per lane: rows
-    // padded to whole 256-column waves of that shape (padding columns are dead: zero coefficients, zero state)
-    tc_ok_ = block && tc_mode_ >= 0;
-    if (tc_ok_) m_pad_ = (m_pad_ + 255) / 256 * 256;
-    // teams, grouped into size classes (one launch of the oscillator bank per team size, largest
-    // first); the SoA rows stay m_pad wide and a team touches its own columns only
-    {
-        // Team size.  A full chip (>= 4096 waves) runs whole objects as teams of up to 16 waves.  Below
-        // that the launch is bound by the per-sample latency of a wave, which is shortest when the
-        // wave shares its SIMD / CU with as few others as possible (measured: 8 x 4096 modes 425 -> 570 x
-        // real time with 2-wave teams, 1 x 512 modes 778 -> 822 x with 1-wave teams): spread the waves
-        // evenly over the 256 CUs.
-        const int team_max = block ? MAX_WAVES_PER_BLOCK_TEAM : MAX_WAVES_PER_TEAM;
-        int team_cap = (int)std::min<long long>(team_max, std::max<long long>(1, (total_waves(R) + n_cus_ - 1) / n_cus_));
-        if (desc_.team_waves > 0) team_cap = std::min(team_max, desc_.team_waves);
-        std::vector<std::vector<TeamDesc>> by_w(MAX_WAVES_PER_TEAM + 1);
-        std::vector<SplitObj> split;
-        n_part_rows_ = 0;
-        W_ = 1;
-        for (int i = 0; i < N; ++i) {
-            const int w = waves_of(objs_[i], R);
-            const int parts = (w + team_cap - 1) / team_cap;
-            const int base = w / parts, rem = w % parts;
-            int w0 = 0;
-            if (parts > 1) {
-                SplitObj so = {i, n_part_rows_, parts, 0};
-                split.push_back(so);
-            }
-            for (int pi = 0; pi < parts; ++pi) {
-                const int wp = base + (pi < rem ? 1 : 0);
-                TeamDesc td = {i, 64 * R * w0, parts > 1 ? n_part_rows_++ : -1, 0};
-                by_w[wp].push_back(td);
-                W_ = std::max(W_, wp);
-                w0 += wp;
-            }
-        }
-        classes_.clear();
-        std::vector<TeamDesc> flat;
-        for (int w = MAX_WAVES_PER_TEAM; w >= 1; --w) {
-            if (by_w[w].empty()) continue;
-            SizeClass c;
-            c.W = w;
-            c.first = (int)flat.size();
-            c.count = (int)by_w[w].size();
-            flat.insert(flat.end(), by_w[w].begin(), by_w[w].end());
-            classes_.push_back(c);
-        }
-        for (size_t k = 0; k < flat.size(); ++k) flat[k].id = (int)k;
-        n_teams_ = (int)flat.size();
-        total_team_waves_ = total_waves(R);
-        if (classes_.size() > 1 && !ev_fork_) {
-            HIPTRY(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-            for (int i = 0; i < N_CLASS_STREAMS; ++i) {
-                HIPTRY(hipStreamCreateWithFlags(&class_stream_[i], hipStreamNonBlocking));
-                HIPTRY(hipEventCreateWithFlags(&ev_join_[i], hipEventDisableTiming));
-            }
-        }
-        n_split_ = (int)split.size();
-        HIPTRY(d_teams_.ensure(flat.size()));
-        HIPTRY(hipMemcpy(d_teams_.p, flat.data(), flat.size() * sizeof(TeamDesc), hipMemcpyHostToDevice));
-        if (n_split_) {
-            HIPTRY(d_split_.ensure(split.size()));
-            HIPTRY(hipMemcpy(d_split_.p, split.data(), split.size() * sizeof(SplitObj), hipMemcpyHostToDevice));
-        }
-    }
-
-    if (tc_ok_) {
-        // team tables of the time-chunked launches, one per shape: whole objects as teams of up to 8 waves (an object that
-        // needs more is cut into several teams whose partial sums sum_parts adds, as above)
-        const int shapes[3] = {1, 2, 4};
-        for (int k = 0; k < 3; ++k) {
-            TcSet &ts = tc_[k];
-            ts.R = shapes[k];
-            std::vector<std::vector<TeamDesc>> by_w(MAX_WAVES_PER_BLOCK_TEAM + 1);
-            std::vector<SplitObj> split;
-            ts.n_part_rows = 0;
-            ts.waves = 0;
-            ts.cover = 0;
-            const int tcap_desc = desc_.team_waves > 0 ? std::min(MAX_WAVES_PER_BLOCK_TEAM, desc_.team_waves) : MAX_WAVES_PER_BLOCK_TEAM;
-            int wmax_set = 1;
-            for (int i = 0; i < N; ++i) {
-                const int w = waves_of(objs_[i], ts.R);
-                // One mode per lane: an object that needs several teams anyway gets teams of FOUR waves -- three such workgroups
-                // fit a CU's LDS (twelve waves, three per SIMD; one team of eight leaves it at two per SIMD), and these builds are
-                // bound by what a wave does between its matrix bursts, not by the matrix pipe (8 x 4096 sustained scraping).
-                const int tcap = (ts.R == 1 && w > MAX_WAVES_PER_BLOCK_TEAM && desc_.team_waves <= 0) ? 4 : tcap_desc;
-                wmax_set = std::max(wmax_set, std::min(w, tcap));
-                const int parts = (w + tcap - 1) / tcap;
-                const int base = w / parts, rem = w % parts;
-                int w0 = 0;
-                if (parts > 1) {
-                    SplitObj so = {i, ts.n_part_rows, parts, 0};
-                    split.push_back(so);
-                }
-                for (int pi = 0; pi < parts; ++pi) {
-                    const int wp = base + (pi < rem ? 1 : 0);
-                    TeamDesc td = {i, 64 * ts.R * w0, parts > 1 ? ts.n_part_rows++ : -1, 0};
-                    by_w[wp].push_back(td);
-                    w0 += wp;
-                }
-                ts.waves += w;
-                ts.cover += (long long)w * 64 * ts.R;
-            }
-            ts.classes.clear();
-            std::vector<TeamDesc> flat;
-            for (int w = MAX_WAVES_PER_BLOCK_TEAM; w >= 1; --w) {
-                if (by_w[w].empty()) continue;
-                SizeClass c;
-                c.W = w;
-                c.first = (int)flat.size();
-                c.count = (int)by_w[w].size();
-                flat.insert(flat.end(), by_w[w].begin(), by_w[w].end());
-                ts.classes.push_back(c);
-            }
-            for (size_t j = 0; j < flat.size(); ++j) flat[j].id = (int)j;
-            ts.n_teams = (int)flat.size();
-            ts.n_split = (int)split.size();
-            {
-                // waves of this shape a CU holds at once: two 256-register waves per SIMD for two and four modes per lane; one mode
-                // per lane: three per SIMD by its registers, as many whole workgroups as the LDS takes (allocated in 1280-byte granules)
-                ts.waves_per_cu = 8;
-                if (ts.R == 1) {
-                    const size_t lds = (block_lds_bytes(wmax_set, 1) + 1279) / 1280 * 1280;
-                    ts.waves_per_cu = (int)std::max<size_t>(wmax_set, std::min<size_t>(12, (160 * 1024 / lds) * wmax_set));
-                }
-            }
-            HIPTRY(ts.d_teams.ensure(flat.size()));
-            HIPTRY(hipMemcpy(ts.d_teams.p, flat.data(), flat.size() * sizeof(TeamDesc), hipMemcpyHostToDevice));
-            if (ts.n_split) {
-                HIPTRY(ts.d_split.ensure(split.size()));
-                HIPTRY(hipMemcpy(ts.d_split.p, split.data(), split.size() * sizeof(SplitObj), hipMemcpyHostToDevice));
-            }
-        }
-    }
-
-    // K1p: fewer than one wave of oscillators per SIMD even with one mode per lane -- a team of several waves per 64
-    // modes instead (kernels_pipe.hip: a producer and two consumers).  f32 block form only; desc.bank_kernel = BLOCK keeps
-    // the one-wave-per-64-modes kernel (and its time chunks, K5) for every launch.
-    {
-        split_ok_ = false;
-        long long chunks = 0;
-        for (const Object &o : objs_) chunks += std::max(1, (o.n_modes + 63) / 64);
-        const long long max_chunks = desc_.pipe_max_teams > 0 ? desc_.pipe_max_teams : 2LL * n_cus_;
-        if (block && form_ == PBSO_FORM_BLOCK && R_ == 1 && chunks <= max_chunks && desc_.bank_kernel != PBSO_BANK_BLOCK) {
-            std::vector<TeamDesc> ts;
-            std::vector<SplitObj> tsplit;
-            n_ts_part_rows_ = 0;
-            for (int i = 0; i < N; ++i) {
-                const int parts = std::max(1, (objs_[i].n_modes + 63) / 64);
-                if (parts > 1) {
-                    SplitObj so = {i, n_ts_part_rows_, parts, 0};
-                    tsplit.push_back(so);
-                }
-                for (int c = 0; c < parts; ++c) {
-                    TeamDesc td = {i, 64 * c, parts > 1 ? n_ts_part_rows_++ : -1, (int)ts.size()};
-                    ts.push_back(td);
-                }
-            }
-            n_ts_teams_ = (int)ts.size();
-            n_ts_split_ = (int)tsplit.size();
-            HIPTRY(d_ts_teams_.ensure(ts.size()));
-            HIPTRY(hipMemcpy(d_ts_teams_.p, ts.data(), ts.size() * sizeof(TeamDesc), hipMemcpyHostToDevice));
-            if (n_ts_split_) {
-                HIPTRY(d_ts_split_.ensure(tsplit.size()));
-                HIPTRY(hipMemcpy(d_ts_split_.p, tsplit.data(), tsplit.size() * sizeof(SplitObj), hipMemcpyHostToDevice));
-            }
-            split_ok_ = true;
-            split_always_ = desc_.bank_kernel == PBSO_BANK_PIPE;
-        }
-    }
-
-    const size_t nm = (size_t)N * m_pad_;
-    std::vector<float> ca(nm, 0.f), cb(nm, 0.f);
-    std::vector<double> c3(nm, 0.0);
-    std::vector<int> nmodes(N);
-    for (int i = 0; i < N; ++i) {
-        const Object &o = objs_[i];
-        nmodes[i] = o.n_modes;
-        for (int m = 0; m < o.n_modes; ++m) {
-            const size_t k = (size_t)i * m_pad_ + m;
-            if (form_ != PBSO_FORM_DIRECT) {
-                ca[k] = (float)(-o.c2[m]);                     // eps^2
-                cb[k] = -(float)((1.0 - o.c1[m]) - o.c2[m]);   // -e, e = |1 - z|^2 = 1 - c1 - c2 (stored negated:
-                                                               //  d = eps^2 d + (-e) q is then a plain v_fmac)
-            } else {
-                ca[k] = (float)o.c1[m];
-                cb[k] = (float)o.c2[m];
-            }
-            c3[k] = o.c3[m];
-        }
-    }
-    HIPTRY(d_ca_.ensure(nm));
-    HIPTRY(d_cb_.ensure(nm));
-    HIPTRY(d_sq_.ensure(nm));
-    HIPTRY(d_sd_.ensure(nm));
-    HIPTRY(d_ss_.ensure(nm));
-    HIPTRY(d_c3_.ensure(nm));
-    HIPTRY(d_n_modes_.ensure(N));
-    HIPTRY(hipMemcpy(d_ca_.p, ca.data(), nm * sizeof(float), hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_cb_.p, cb.data(), nm * sizeof(float), hipMemcpyHostToDevice));
-    HIPTRY(hipMemset(d_sq_.p, 0, nm * sizeof(float)));
-    HIPTRY(hipMemset(d_sd_.p, 0, nm * sizeof(float)));
-    HIPTRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_ss_.p), 0x3F800000, nm));      // scale 1.0f: state stored unscaled
-    HIPTRY(hipMemcpy(d_c3_.p, c3.data(), nm * sizeof(double), hipMemcpyHostToDevice));
-    if (desc_.qnorm_mode == PBSO_QNORM_CLOSED || (block && desc_.qnorm_mode != PBSO_QNORM_OFF)) {
-        int rc = build_gq();
-        if (rc != PBSO_OK) return rc;
-    }
-
-    if (block) {
-        // Block form: per mode the one-sample matrix in the basis x = (q, q - q_prev) is
-        // A = [[1 - e, eps^2], [-e, eps^2]] (e = 1 - c1 - c2, eps^2 = -c2).  Row 0 of A^j, j = 1..16, gives the
-        // output weights (a_j, b_j); P = A^16 advances the state by one block.  All in fp64, rounded once.
-        // P11 is stored as P11 - 1 (q' = q + (P11 - 1) q + P12 d keeps the small angle of low modes).
-        std::vector<float> pc(4 * nm, 0.f), wt((size_t)nm / 2 * 64, 0.f);
-        for (int i = 0; i < N; ++i) {
-            const Object &o = objs_[i];
-            for (int m = 0; m < o.n_modes; ++m) {
-                const double eps2 = -o.c2[m], e = (1.0 - o.c1[m]) - o.c2[m];
-                const double a00 = 1.0 - e, a01 = eps2, a10 = -e, a11 = eps2;
-                double p00 = 1, p01 = 0, p10 = 0, p11 = 1;                 // A^j, starting from I
-                const size_t k = (size_t)i * m_pad_ + m;
-                float *w = wt.data() + (k / 2) * 64 + 16 * (2 * (k & 1));  // lane = 16 * (2 * mode-of-pair + comp) + (j - 1)
-                for (int j = 1; j <= BLOCK_J; ++j) {
-                    const double n00 = a00 * p00 + a01 * p10, n01 = a00 * p01 + a01 * p11;
-                    const double n10 = a10 * p00 + a11 * p10, n11 = a10 * p01 + a11 * p11;
-                    p00 = n00; p01 = n01; p10 = n10; p11 = n11;
-                    w[j - 1] = (float)p00;
-                    w[16 + j - 1] = (float)p01;
-                }
-                pc[k] = (float)(p00 - 1.0);
-                pc[nm + k] = (float)p01;
-                pc[2 * nm + k] = (float)p10;
-                pc[3 * nm + k] = (float)p11;
-            }
-        }
-        if (form_ == PBSO_FORM_BLOCK_BF16) {
-            // Split-bf16 operand table: per group of 16 columns 8 rows of 64 dwords, rows 0..3 the hi parts, 4..7 the
-            // lo parts; lane l = 16 kq + (j - 1), dword dd <-> mode 16 G + 4 kq + dd: low half a_j, high half b_j (the k
-            // order of v_mfma_f32_16x16x32_bf16: k = 8 kq + 2 dd + comp).  hi = bf16(x) round-to-nearest-even,
-            // lo = bf16(x - hi).
-            auto bf16_rne = [](float x) -> uint32_t {
-                uint32_t u;
-                std::memcpy(&u, &x, 4);
-                if ((u & 0x7F800000u) == 0x7F800000u) return u >> 16;                 // inf / nan
-                return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-            };
-            auto split = [&](double x, uint32_t &hi, uint32_t &lo) {
-                const float xf = (float)x;
-                hi = bf16_rne(xf);
-                const uint32_t hb = hi << 16;
-                float hf;
-                std::memcpy(&hf, &hb, 4);
-                lo = bf16_rne(xf - hf);
-            };
-            std::vector<float> wf(wt);                                               // the f32 table just built
-            std::vector<uint32_t> w16(wt.size(), 0u);
-            for (size_t G = 0; G < nm / 16; ++G)
-                for (int l = 0; l < 64; ++l) {
-                    const int j = l & 15, kq = l >> 4;
-                    for (int dd = 0; dd < 4; ++dd) {
-                        const size_t col = 16 * G + 4 * kq + dd;                      // flat column index (object * m_pad + column)
-                        // f32 table: row col / 2, lane 16 * (2 * (col & 1) + comp) + j
-                        const float a = wf[(col / 2) * 64 + 16 * (2 * (col & 1) + 0) + j];
-                        const float b = wf[(col / 2) * 64 + 16 * (2 * (col & 1) + 1) + j];
-                        uint32_t ah, al, bh, bl;
-                        split((double)a * TRUNC_SPLIT_GAIN, ah, al);
-                        split((double)b * TRUNC_SPLIT_GAIN, bh, bl);
-                        w16[(8 * G + dd) * 64 + l] = ah | (bh << 16);
-                        w16[(8 * G + 4 + dd) * 64 + l] = al | (bl << 16);
-                    }
-                }
-            std::memcpy(wt.data(), w16.data(), wt.size() * sizeof(float));
-        }
-        HIPTRY(d_pc_.ensure(4 * nm));
-        HIPTRY(hipMemcpy(d_pc_.p, pc.data(), 4 * nm * sizeof(float), hipMemcpyHostToDevice));
-        if (tc_ok_) {
-            // K5: a whole buffer as one step of the state -- A^B (first entry minus one, as P) and A^(B-1) u, u = (1, 1)': what a
-            // force sample at the buffer's first sample leaves at its end.  fp64, rounded once.
-            std::vector<float> sc(6 * nm, 0.f);
-            for (int i = 0; i < N; ++i) {
-                const Object &o = objs_[i];
-                for (int m = 0; m < o.n_modes; ++m) {
-                    const double eps2 = -o.c2[m], e = (1.0 - o.c1[m]) - o.c2[m];
-                    const double a00 = 1.0 - e, a01 = eps2, a10 = -e, a11 = eps2;
-                    double p00 = 1, p01 = 0, p10 = 0, p11 = 1;
-                    const size_t k = (size_t)i * m_pad_ + m;
-                    for (int j = 1; j <= B_; ++j) {
-                        if (j == B_) {                                   // A^(B-1) u
-                            sc[4 * nm + k] = (float)(p00 + p01);
-                            sc[5 * nm + k] = (float)(p10 + p11);
-                        }
-                        const double n00 = a00 * p00 + a01 * p10, n01 = a00 * p01 + a01 * p11;
-                        const double n10 = a10 * p00 + a11 * p10, n11 = a10 * p01 + a11 * p11;
-                        p00 = n00; p01 = n01; p10 = n10; p11 = n11;
-                    }
-                    sc[k] = (float)(p00 - 1.0);
-                    sc[nm + k] = (float)p01;
-                    sc[2 * nm + k] = (float)p10;
-                    sc[3 * nm + k] = (float)p11;
-                }
-            }
-            HIPTRY(d_scan_.ensure(6 * nm));
-            HIPTRY(hipMemcpy(d_scan_.p, sc.data(), 6 * nm * sizeof(float), hipMemcpyHostToDevice));
-        }
-        // (a time-chunked launch picks its own team shape: one or two modes per lane use the table; K5's dense_increment_kernel
-        //  uses it whatever the projection and the bank's own path for dense buffers are)
-        ftab_forced_ = form_ == PBSO_FORM_BLOCK && (R_ <= 2 || tc_ok_) && forced_block_;
-        if (ftab_forced_ || tc_ok_) {
-            // Forced block path without qnorm rows (kernels_block.hip, FT): a force sample f enters the state as f u, u = (1, 1)'
-            // (d += f, q += d), so the samples 16 n + i, i = 1..16, of a dense profile move the next block-start state by
-            // sum_i A^(16 - i) u f_i.  Plane 2 i' + c holds component c of A^(15 - i') u, i' = 0..15, per mode (fp64, rounded once).
-            // Engines with more than two modes per lane keep the per-sample path (no registers left for 32 constants per mode).
-            std::vector<float> ft((size_t)32 * nm, 0.f);
-            for (int i = 0; i < N; ++i) {
-                const Object &o = objs_[i];
-                for (int m = 0; m < o.n_modes; ++m) {
-                    const double eps2 = -o.c2[m], e = (1.0 - o.c1[m]) - o.c2[m];
-                    double v0 = 1.0, v1 = 1.0;                              // A^delta u, delta = 0, 1, ...
-                    const size_t k = (size_t)i * m_pad_ + m;
-                    for (int delta = 0; delta < BLOCK_J; ++delta) {
-                        const int ip = BLOCK_J - 1 - delta;                // in-block sample index (0-based) this power belongs to
-                        ft[(size_t)(2 * ip) * nm + k] = (float)v0;
-                        ft[(size_t)(2 * ip + 1) * nm + k] = (float)v1;
-                        const double n0 = (1.0 - e) * v0 + eps2 * v1, n1 = -e * v0 + eps2 * v1;
-                        v0 = n0; v1 = n1;
-                    }
-                }
-            }
-            HIPTRY(d_ftab_.ensure(ft.size()));
-            HIPTRY(hipMemcpy(d_ftab_.p, ft.data(), ft.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        HIPTRY(d_wtab_.ensure(wt.size()));
-        HIPTRY(hipMemcpy(d_wtab_.p, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-
-    // mode shapes: mode-major (ModeData.h:24) -> vertex-major [dof][m_pad]
-    {
-        std::vector<long long> off(N, 0);
-        size_t total = 0;
-        for (int i = 0; i < N; ++i) {
-            off[i] = (long long)total;
-            total += (size_t)objs_[i].n_dof * m_pad_;
-        }
-        HIPTRY(d_shape_off_.ensure(N));
-        HIPTRY(hipMemcpy(d_shape_off_.p, off.data(), N * sizeof(long long), hipMemcpyHostToDevice));
-        std::vector<long long> row_off(N, 0);
-        for (int i = 0; i < N; ++i) row_off[i] = off[i] / m_pad_;
-        HIPTRY(d_g32_off_.ensure(N));
-        HIPTRY(hipMemcpy(d_g32_off_.p, row_off.data(), N * sizeof(long long), hipMemcpyHostToDevice));
-        HIPTRY(d_g32_.ensure(std::max<size_t>(total, 1)));
-        if (total) {
-            HIPTRY(d_shapes_.ensure(total));
-            std::vector<double> vm;
-            std::vector<float> vg;
-            for (int i = 0; i < N; ++i) {
-                Object &o = objs_[i];
-                if (!o.n_dof) continue;
-                vm.assign((size_t)o.n_dof * m_pad_, 0.0);
-                vg.assign((size_t)o.n_dof * m_pad_, 0.f);
-                for (int m = 0; m < o.n_modes; ++m)
-                    for (int dof = 0; dof < o.n_dof; ++dof) {
-                        const double u = o.shapes[(size_t)m * o.n_dof + dof];
-                        vm[(size_t)dof * m_pad_ + m] = u;
-                        vg[(size_t)dof * m_pad_ + m] = (float)(o.c3[m] * u);
-                    }
-                HIPTRY(hipMemcpy(d_shapes_.p + off[i], vm.data(), vm.size() * sizeof(double), hipMemcpyHostToDevice));
-                HIPTRY(hipMemcpy(d_g32_.p + off[i], vg.data(), vg.size() * sizeof(float), hipMemcpyHostToDevice));
-                std::vector<double>().swap(o.shapes);
-            }
-        }
-    }
-    // FFAT maps
-    {
-        std::vector<long long> goff(N, 0);
-        std::vector<FfatGeom> geom;
-        std::vector<double> psi;
-        for (int i = 0; i < N; ++i) {
-            Object &o = objs_[i];
-            o.maps_cover_modes = true;
-            for (int m = 0; m < o.n_modes; ++m)
-                if (m >= (int)o.geom.size() || !o.geom[m].valid) { o.maps_cover_modes = false; break; }
-            goff[i] = (long long)geom.size();
-            const int ng = std::min((int)o.geom.size(), m_pad_);
-            nmodes[i] = o.n_modes;
-            for (int m = 0; m < ng; ++m) {
-                FfatGeom g = o.geom[m];
-                g.psi_off += (long long)psi.size();
-                geom.push_back(g);
-            }
-            // pad so that every mode < n_modes has an entry
-            for (int m = ng; m < o.n_modes; ++m) {
-                FfatGeom z;
-                std::memset(&z, 0, sizeof(z));
-                geom.push_back(z);
-            }
-            psi.insert(psi.end(), o.psi.begin(), o.psi.end());
-            std::vector<double>().swap(o.psi);
-        }
-        HIPTRY(d_geom_off_.ensure(N));
-        HIPTRY(hipMemcpy(d_geom_off_.p, goff.data(), N * sizeof(long long), hipMemcpyHostToDevice));
-        geom_off_h_ = goff;
-        if (!geom.empty()) {
-            HIPTRY(d_geom_.ensure(geom.size()));
-            HIPTRY(hipMemcpy(d_geom_.p, geom.data(), geom.size() * sizeof(FfatGeom), hipMemcpyHostToDevice));
-        }
-        if (!psi.empty()) {
-            HIPTRY(d_psi_.ensure(psi.size()));
-            HIPTRY(hipMemcpy(d_psi_.p, psi.data(), psi.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        // Objects whose valid modes all carry ONE geometry (a map file's header: box, centre, cell size, face layout) -- every scene
-        // we know of: the maps of an object are made over the same box -- get their maps a second time, transposed, and their listener
-        // events the kernel that locates a position once per event (kernels_exact.hip, ffat_lookup_shared_kernel).  Compared field by
-        // field, bit for bit; a single differing mode keeps the object on the general kernels.  PBSO_FFAT_SHARED=0: never.
-        {
-            const char *env = std::getenv("PBSO_FFAT_SHARED");
-            const bool want = !(env && std::atoi(env) == 0);
-            std::vector<FfatShared> shared(N);
-            std::memset(shared.data(), 0, shared.size() * sizeof(FfatShared));
-            std::vector<double> mode_k(geom.size(), 0.0), psi_t;
-            std::vector<int> mode_valid(geom.size(), 0);
-            ffat_shared_h_.assign(N, 0);
-            n_ffat_shared_ = 0;
-            auto same_geometry = [](const FfatGeom &a, const FfatGeom &b) {
-                return a.n_psi == b.n_psi && !std::memcmp(&a.cell_size, &b.cell_size, sizeof(double)) &&
-                       !std::memcmp(a.center3, b.center3, sizeof(a.center3)) && !std::memcmp(a.low_corners, b.low_corners, sizeof(a.low_corners)) &&
-                       !std::memcmp(a.center, b.center, sizeof(a.center)) && !std::memcmp(a.bbox_low, b.bbox_low, sizeof(a.bbox_low)) &&
-                       !std::memcmp(a.bbox_top, b.bbox_top, sizeof(a.bbox_top)) && !std::memcmp(a.n_elements, b.n_elements, sizeof(a.n_elements)) &&
-                       !std::memcmp(a.strides, b.strides, sizeof(a.strides));
-            };
-            for (int i = 0; i < N && want; ++i) {
-                const Object &o = objs_[i];
-                const FfatGeom *g = geom.data() + goff[i];
-                const int ng = (int)((i + 1 < N ? goff[i + 1] : (long long)geom.size()) - goff[i]);
-                const int nm = std::min(o.n_modes, ng);
-                int first = -1, n_valid = 0;
-                bool same = true;
-                for (int m = 0; m < nm && same; ++m) {
-                    if (!g[m].valid) continue;
-                    if (first < 0) first = m;
-                    else same = same_geometry(g[first], g[m]);
-                    n_valid += 1;
-                }
-                if (!same || first < 0 || n_valid < 2) continue;          // (one map: nothing to share)
-                const int pitch = (nm + 15) / 16 * 16;
-                const size_t n_psi = (size_t)g[first].n_psi;
-                shared[i].psit_off = (long long)psi_t.size();
-                shared[i].pitch = pitch;
-                shared[i].first_valid = first;
-                psi_t.resize(psi_t.size() + n_psi * pitch, 0.0);
-                double *dst = psi_t.data() + shared[i].psit_off;
-                for (size_t c0 = 0; c0 < n_psi; c0 += 512)          // (blocks of cells: the strided writes of one block stay in cache)
-                    for (int m = 0; m < nm; ++m) {
-                        if (!g[m].valid) continue;
-                        const double *src = psi.data() + g[m].psi_off;
-                        for (size_t c = c0; c < std::min(n_psi, c0 + 512); ++c) dst[c * pitch + m] = src[c];
-                    }
-                ffat_shared_h_[i] = 1;
-                n_ffat_shared_ += 1;
-            }
-            for (size_t j = 0; j < geom.size(); ++j) { mode_k[j] = geom[j].k; mode_valid[j] = geom[j].valid; }
-            if (n_ffat_shared_ > 0) {
-                HIPTRY(d_ffat_shared_.ensure(N));
-                HIPTRY(hipMemcpy(d_ffat_shared_.p, shared.data(), N * sizeof(FfatShared), hipMemcpyHostToDevice));
-                HIPTRY(d_ffat_k_.ensure(mode_k.size()));
-                HIPTRY(hipMemcpy(d_ffat_k_.p, mode_k.data(), mode_k.size() * sizeof(double), hipMemcpyHostToDevice));
-                HIPTRY(d_ffat_valid_.ensure(mode_valid.size()));
-                HIPTRY(hipMemcpy(d_ffat_valid_.p, mode_valid.data(), mode_valid.size() * sizeof(int), hipMemcpyHostToDevice));
-                HIPTRY(d_psi_t_.ensure(psi_t.size()));
-                HIPTRY(hipMemcpy(d_psi_t_.p, psi_t.data(), psi_t.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-        }
-    }
-    HIPTRY(hipMemcpy(d_n_modes_.p, nmodes.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    HIPTRY(d_board_.ensure(4096));
-    HIPTRY(hipMemset(d_board_.p, 0, 4096 * sizeof(unsigned)));
-    // transfer rows: [0,N) _latest_transfer, [N,2N) the 1-slot transfer queue, then per-launch scratch
-    HIPTRY(d_xfer_.ensure((size_t)2 * N * m_pad_));
-    HIPTRY(hipMemset(d_xfer_.p, 0, (size_t)2 * N * m_pad_ * sizeof(double)));
-    (void)warm_copy_engines();
-    if (desc_.submit_thread > 0) submit_ = new SubmitQueue(desc_.device);
-    finalized_ = true;
-    return PBSO_OK;
-}
-
-// One-time work of the runtime that would otherwise block a step's submission, done here, untimed (PBSO_WARM_COPIES=0: not).
-// Found with PBSO_TIMELINE=1 / scripts/debug/r03_stalls.py: an engine's first ~30 launches contained two hipMemcpyAsync calls
-// (the step's ONE upload) that took 6 - 7 ms each whatever their size, with no buffer growing -- in the middle of a real-time run,
-// or of a 20-step timed region (64 x 256 with a listener move per buffer measured 2800 x or 4900 x run to run, depending on
-// whether one fell into the 40 timed steps).  (1) The runtime opens its copy queues lazily: a few overlapping uploads and
-// read-backs on both streams remove the first.  (2) The other comes with the first upload whose stream is still WAITING for an
-// event of the other stream when the call is made -- which is what a step's upload looks like as soon as the host runs a whole
-// plan set ahead of the oscillator bank (the wait for ev_k1_done_ in front of it); it happened at a random launch, whenever the
-// host first got that far ahead.  Issuing exactly that pattern here removes it.
-int Engine::warm_copy_engines() {
-    if (desc_.warm_copies < 0) return PBSO_OK;
-    // Best effort: a failure here costs a slow first launch, never the engine (errors are swallowed, everything is released).
-    // A caller's stream is not touched: the second pattern only needs SOME stream the preparation stream waits for.
-    constexpr size_t chunk = (size_t)1 << 20;
-    const int n = 6;
-    PinBuf<unsigned char> h;
-    DevBuf<unsigned char> d;
-    hipStream_t other = own_stream_ ? stream_ : nullptr;
-    hipEvent_t ev = nullptr, ev2 = nullptr;
-    auto body = [&]() -> hipError_t {
-        hipError_t e;
-        if (!other && (e = hipStreamCreateWithFlags(&other, hipStreamNonBlocking)) != hipSuccess) return e;
-        if ((e = h.ensure(chunk * n)) != hipSuccess) return e;
-        if ((e = d.ensure(chunk * n)) != hipSuccess) return e;
-        std::memset(h.p, 0, chunk * n);
-        for (int rep = 0; rep < 2; ++rep) {           // (1) the copy queues, both directions, both streams
-            for (int i = 0; i < n; ++i)
-                if ((e = hipMemcpyAsync(d.p + chunk * i, h.p + chunk * i, chunk, hipMemcpyHostToDevice, (i & 1) ? other : prep_stream_)) != hipSuccess) return e;
-            for (int i = 0; i < n; ++i)
-                if ((e = hipMemcpyAsync(h.p + chunk * i, d.p + chunk * i, chunk, hipMemcpyDeviceToHost, (i & 1) ? prep_stream_ : other)) != hipSuccess) return e;
-        }
-        if ((e = hipStreamSynchronize(prep_stream_)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(other)) != hipSuccess) return e;
-        // (2) uploads behind a wait for an event that has not happened yet
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-        if ((e = hipEventCreateWithFlags(&ev2, hipEventDisableTiming)) != hipSuccess) return e;
-        for (int rep = 0; rep < 4; ++rep) {
-            for (int i = 0; i < n; ++i)
-                if ((e = hipMemcpyAsync(d.p + chunk * i, h.p + chunk * i, chunk, hipMemcpyHostToDevice, other)) != hipSuccess) return e;
-            if ((e = hipEventRecord(ev, other)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(prep_stream_, ev, 0)) != hipSuccess) return e;
-            if ((e = hipMemcpyAsync(d.p, h.p, (size_t)384 << 10, hipMemcpyHostToDevice, prep_stream_)) != hipSuccess) return e;
-            if ((e = hipEventRecord(ev2, prep_stream_)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(other, ev2, 0)) != hipSuccess) return e;
-        }
-        if ((e = hipStreamSynchronize(prep_stream_)) != hipSuccess) return e;
-        return hipStreamSynchronize(other);
-    };
-    (void)body();
-    (void)hipGetLastError();
-    if (prep_stream_) (void)hipStreamSynchronize(prep_stream_);
-    if (other) (void)hipStreamSynchronize(other);
-    if (ev) (void)hipEventDestroy(ev);
-    if (ev2) (void)hipEventDestroy(ev2);
-    if (other && other != stream_) (void)hipStreamDestroy(other);
-    h.release();
-    d.release();
     return PBSO_OK;
 }
 
@@ -2470,743 +1733,6 @@ void Engine::build_ar_tables() {
     }
 }
 
-// ---------------------------------------------------------------------------
-// One step = nb buffers for every object.  Long steps are cut into launches of at most
-// chunk_buffers_ buffers so that the host plans chunk c+1 while the device runs chunk c (the same
-// overlap consecutive steps have); results do not depend on the cut (state, force lists and queues
-// carry over exactly as between steps).
-// K5: does this launch run time-chunked, with which team shape and how many buffers per chunk?  Auto: only while the scene
-// leaves SIMDs idle (fewer than two waves per SIMD in its largest shape) and few of the launch's (object, buffer) pairs
-// carry a dense force profile (the scan steps those per sample, serially per object).  The shape: the most modes per lane
-// that still fills the chip when every buffer is its own chunk (a wave of four modes per lane amortises its operand table
-// over more work), unless the padding to whole waves wastes columns; the chunk length minimises rounds x (length + start-up).
-bool Engine::choose_time_chunks(int nb, int n_dense_rows, int *set, int *cb) const {
-    if (!tc_ok_ || !d_scan_.p || (nb < 2 && tc_mode_ <= 0)) return false;
-    if (n_dump_ > 0) return false;                       // (objects that keep their block-start states for a listener mix: the walk in buffer order, as K1p)
-    const long long N = (long long)objs_.size();
-    // Dense-profile buffers (Gaussian / AR, sustained contact: forces.h:92-128, modal_solver.h:222-240) take their place in the scan
-    // through their increments (dense_increment_kernel); the bank steps them in its forced block path.
-    if (n_dense_rows > 0 && !d_ftab_.p) return false;
-    // (engines whose bank steps dense buffers per sample -- the split-bf16 projection, forced_block < 0 -- keep their launches with
-    //  many of them on the kernels that walk the buffers in order, as before round 5)
-    if (tc_mode_ == 0 && !ftab_forced_ && (long long)n_dense_rows * 8 > N * nb) return false;
-    // (every dense row costs m_pad x 8 bytes of increments per plan set: a launch whose rows would take more than 1 GiB walks its
-    //  buffers in order instead -- 1024 x 512 sustained scraping in ten-second steps is 880 640 rows = 3.6 GB)
-    if ((long long)n_dense_rows * m_pad_ * 8 > (1LL << 30)) return false;
-    const bool dense_majority = (long long)n_dense_rows * 2 > N * nb;
-    // (a scene small enough for the pipeline kernel keeps its mostly-dense launches WITHOUT qnorm rows there: teams of five waves per
-    //  64 modes walk the buffers in order and evaluate every increment once -- cut in time they are evaluated twice, for the scan and
-    //  in the bank: 8 x 4096 x 86 scraping 0.25 ms per step against 0.27.  With qnorm rows the re-stepped samples are the long stage
-    //  and want the whole chip's vector ALUs at three waves per SIMD: cut in time 0.33 ms, five-wave teams 0.49, three-wave teams 0.45)
-    if (dense_majority && tc_mode_ == 0 && use_split() && ftab_forced_ && k2_rows_launch_ && desc_.qnorm_mode == PBSO_QNORM_OFF) return false;
-    int k = 0;
-    for (int c = 2; c >= 1; --c)
-        if (tc_[c].cover * 100 <= tc_[0].cover * 115 && tc_[c].waves * nb >= (long long)tc_[c].waves_per_cu * n_cus_) { k = c; break; }
-    // a launch of mostly dense buffers: ONE mode per lane -- the only shape whose registers hold the increment table F next to the
-    // operand table W, so that the state moves a block at a time (F . T_n on the matrix pipe) instead of a sample at a time, and
-    // whose per-sample chain for the qnorm rows has three waves per SIMD to hide behind
-    if (dense_majority && ftab_forced_) k = 0;
-    if (tc_shape_ == 1 || tc_shape_ == 2 || tc_shape_ == 4) k = tc_shape_ == 4 ? 2 : tc_shape_ - 1;
-    const long long capacity = (long long)tc_[k].waves_per_cu * n_cus_;
-    const long long waves = tc_[k].waves;
-    int best = nb;
-    if (tc_mode_ > 0) {
-        best = std::min(tc_mode_, nb);
-    } else {
-        // cost of a launch in buffer times: rounds of workgroups x (chunk length + 0.3 for a workgroup's start-up: operand table,
-        // coefficients, state).  A scene LARGER than the chip, whose walk is a launch of several rounds of full-length
-        // workgroups, does not pack perfectly -- a CU may be handed a ninth workgroup while another gets seven
-        // (scripts/census.py 2048: a third, nearly empty round; 1100 / 1536 / 2048 x 512 walk 1.68 / 2.04 / 2.72 ms: half a round
-        // more than their 1.07 / 1.5 / 2 rounds) -- and the shorter the workgroups, the cheaper that tail: such scenes are cut in
-        // time too (1.22 / 1.66 / 2.21 ms).  A scene that fills the chip exactly (1024 x 512: one round) is not.
-        const bool over_full = waves > capacity;
-        // (round 6, ADVICE r05: a mostly-dense scene that fills the chip anyway gains nothing from the cut -- its increments are
-        //  evaluated twice, for the scan and in the bank: 1024 x 512 sustained scraping 7.90 ms per second of audio cut in time against
-        //  7.37 for the walk, profiles/r06_bench_c4scr_*.json -- so the cut is for dense scenes that leave wave slots free)
-        if (dense_majority && waves >= capacity) return false;
-        if (over_full && !dense_majority) {
-            // measured, in rounds of the exactly-full chip (scripts/debug/r04_tcrounds.py): the walk of 1100 / 1536 / 2048 / 3000
-            // objects x 512 modes takes 1.57 / 1.90 / 2.54 / 3.07 -- whole rounds + a last, partly filled one that runs faster the
-            // emptier it is (0.57 + 0.54 x its fill), or half a round of stragglers when the rounds are exactly full -- and the
-            // same scenes cut in time 1.07 x their share of the chip (1.14 / 1.57 / 2.12 / 3.17): at 3000 the walk wins
-            const double frac = (double)waves / (double)capacity, whole = std::floor(frac), fill = frac - whole;
-            const double walk = whole + (fill > 1e-9 ? 0.57 + 0.54 * fill : 0.5);
-            if (frac * 1.07 >= walk) return false;
-        }
-        double best_cost = 0;
-        for (int c = nb; c >= 1; --c) {
-            const long long chunks = (nb + c - 1) / c;
-            const long long rounds = (waves * chunks + capacity - 1) / capacity;
-            const double cost = ((double)rounds + (over_full ? 0.5 : 0.0)) * (c + 0.3);
-            if (c == nb || cost < best_cost - 1e-9) { best = c; best_cost = cost; }
-        }
-    }
-    if ((nb + best - 1) / best < 2 && tc_mode_ <= 0) return false;       // (forced: every launch, so that any cut of a step runs the same arithmetic)
-    *set = k;
-    *cb = best;
-    return true;
-}
-
-int Engine::step(int nb, void *d_audio_user) {
-    HIPTRY(hipSetDevice(desc_.device));      // the caller's thread may have another device current
-    if (!finalized_) return fail(PBSO_ERR_STATE, "step before finalize");
-    if (nb <= 0) return fail(PBSO_ERR_INVALID, "n_buffers must be > 0");
-    if (failed_) return fail(PBSO_ERR_STATE, "an earlier step failed half-way (" + failed_why_ + "): queues and force lists are no "
-                                             "longer consistent, create a new engine");
-    const int N = (int)objs_.size();
-    const bool defer = submit_ != nullptr;             // (GROWTRY: a buffer that grows waits for the recorded calls first)
-    float *audio = (float *)d_audio_user;
-    // outputs of the whole step (growth drains the device first, see DevBuf::ensure)
-    if (!audio) {
-        GROWTRY(d_audio_, (size_t)N * nb * B_, false, stream_);
-        audio = d_audio_.p;
-    }
-    if (desc_.qnorm_mode != PBSO_QNORM_OFF || n_dump_ > 0) GROWTRY(d_qnorm_, (size_t)N * nb * m_pad_, false, stream_);
-    if (n_dump_ > 0) {
-        // block-start states of the objects a multi-listener mix was asked for (pbso_listeners_enable)
-        GROWTRY(d_xdump_, (size_t)n_dump_ * nb * 32 * m_pad_ * 2, false, stream_);
-        GROWTRY(d_xscale_, (size_t)n_dump_ * nb * m_pad_, false, stream_);
-        if (dump_rows_dirty_) {
-            if (defer) { int drc = drain_submit(); if (drc != PBSO_OK) return drc; }
-            GROWTRY(d_dump_row_, N, false, stream_);
-            HIPTRY(hipMemcpyAsync(d_dump_row_.p, dump_row_.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, stream_));
-            HIPTRY(hipStreamSynchronize(stream_));           // (dump_row_ is pageable host memory)
-            dump_rows_dirty_ = false;
-        }
-        dump_nb_ = nb;
-        std::fill(dump_valid_.begin(), dump_valid_.end(), 1);
-    }
-    {
-        // (a step's launches may run on different kernels: room for either kind's partial rows)
-        int rows = std::max(use_split() ? n_ts_part_rows_ : 0, n_part_rows_);
-        if (tc_ok_) for (const TcSet &ts : tc_) rows = std::max(rows, ts.n_part_rows);
-        if (rows) GROWTRY(d_audio_parts_, (size_t)rows * nb * B_, false, stream_);
-    }
-    emitted_.assign((size_t)N * nb, 1);
-    const int64_t step_id = tot_steps_;
-    double plan_ms = 0;
-    for (int b0 = 0; b0 < nb; b0 += chunk_buffers_) {
-        int rc = step_chunk(std::min(chunk_buffers_, nb - b0), b0, nb, audio, step_id);
-        if (rc != PBSO_OK) {
-            // the reference would have aborted here (assert) or be equally stuck (device error)
-            failed_ = true;
-            failed_why_ = err_;
-            return rc;
-        }
-        plan_ms += last_plan_ms_;
-    }
-    last_plan_ms_ = plan_ms;
-    tot_plan_ms_ += plan_ms;
-    tot_steps_ += 1;
-    last_audio_ = audio;
-    last_nb_ = nb;
-    return PBSO_OK;
-}
-
-int Engine::step_chunk(int nb, int b0, int nb_total, float *audio, int64_t step_id) {
-    const int N = (int)objs_.size();
-    PlanSet &ps = set_[cur_set_];
-    plan_b0_ = b0;
-    plan_nb_total_ = nb_total;
-    const auto tw0 = std::chrono::steady_clock::now();
-    // the second submitting thread: this launch's stream calls are recorded (QHIP / QLAUNCH) and handed over at the end
-    const bool defer = submit_ != nullptr;
-    std::vector<SubmitOp> ops;
-    if (defer) {
-        ops.reserve(48);
-        submit_->wait(set_batch_[cur_set_]);             // the launch that last used this plan set has been MADE (its events recorded) ...
-        std::string why;
-        if (submit_->error(&why)) return fail(PBSO_ERR_HIP, "a launch of an earlier step failed on the submitting thread: " + why);
-    }
-    HIPTRY(hipEventSynchronize(ev_set_[cur_set_]));      // ... and this set's previous uploads are done
-    if (stroke_ev_live_[cur_set_]) {                     // PBSO_HOST_PROFILE=1: the stroke kernel of the launch that last used this set
-        float ms = 0.f;
-        HIPTRY(hipEventSynchronize(stroke_ev_[cur_set_][1]));
-        HIPTRY(hipEventElapsedTime(&ms, stroke_ev_[cur_set_][0], stroke_ev_[cur_set_][1]));
-        stroke_kernel_ms_ += ms;
-        stroke_kernel_n_ += 1;
-        stroke_ev_live_[cur_set_] = false;
-    }
-
-    const auto t0 = std::chrono::steady_clock::now();
-    hprof_[0] += std::chrono::duration<double, std::milli>(t0 - tw0).count();
-    int rc = plan(nb);
-    if (rc != PBSO_OK) return rc;
-    // keep _latest_transfer / the transfer queue in their persistent rows after the launch
-    std::vector<int> copy_latest, copy_queued;
-    for (int i : busy_) {
-        Object &o = objs_[i];
-        if (o.latest_row >= 0 && o.latest_row != i) {
-            copy_latest.push_back(o.latest_row);
-            copy_latest.push_back(i);
-            o.latest_row = i;
-        }
-        if (o.trans_full && o.trans_row != N + i) {
-            copy_queued.push_back(o.trans_row);
-            copy_queued.push_back(N + i);
-            o.trans_row = N + i;
-        }
-    }
-    const int n_chains = (int)chain_ptr_.size();
-    const int n_srows = n_stroke_rows_, n_srecs = (int)stroke_recs_.size();
-    const int n_prof_rows = (int)prof_rows_.size() + n_srows;          // (stroke rows: written on the device, behind the host's)
-    const int n_ar_uses = (int)ar_uses_.size() + (k2_rows_launch_ ? n_srows : 0);
-    chain_ptr_.push_back(n_prof_rows);
-    last_plan_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const auto tsub0 = std::chrono::steady_clock::now();
-
-    const int n_frows = n_frows_;
-    last_frows_ = n_frows;
-    last_trows_ = (int64_t)ffat_.size();
-    // Latency path: a short single-launch step submitted while the device is idle (the real-time facade: step, wait, step) has
-    // nothing to run beside -- its preparation goes on the bank's own stream, and the 11 us an event takes to hand a launch
-    // from one stream to the other (profiles/r04_stream_sync.txt) are saved.  Ordering only: same kernels, same arguments.
-    bool one_stream = false;
-    if (latency_path_ && nb == nb_total && nb <= 4 && !defer) {      // (the query below needs the previous launch's events recorded)
-        one_stream = last_set_ < 0 || hipEventQuery(ev_k1_done_[last_set_]) == hipSuccess;      // (the previous bank, hence its preparation)
-        (void)hipGetLastError();
-    }
-    // K5: a launch without (many) dense-profile buffers on a chip the scene cannot fill runs the block kernel as (team, chunk of
-    // buffers) workgroups behind a scan of the buffer-start states (kernels_scan.hip)
-    int tc_set = -1, tc_cb = 0;
-    const bool tc_launch = is_block() && !split_always_ && choose_time_chunks(nb, n_prows_, &tc_set, &tc_cb);
-    hipStream_t sk = stream_, sp = one_stream ? sk : prep_stream_;
-    // (the preparation stream takes over again behind a launch that went without it: behind that launch's bank)
-    if (!one_stream && last_one_stream_ && last_set_ >= 0) QHIP(hipStreamWaitEvent, sp, ev_k1_done_[last_set_], 0);
-    DevBuf<float> &grows = d_grows_[cur_set_];
-    // device arenas (growth drains the device first, see DevBuf::ensure)
-    GROWTRY(d_slots_, std::max<size_t>(1, n_slots_.load()) * m_pad_, true, sp);
-    GROWTRY(grows, std::max<size_t>(1, (size_t)n_frows) * m_pad_, false, sp);
-    const bool qn = desc_.qnorm_mode != PBSO_QNORM_OFF;
-
-    {
-        int hrc = harvest_timing(ev_pending_.size() >= 256);      // (what has finished; everything when too many events are live)
-        if (hrc != PBSO_OK) return hrc;
-    }
-    EvQuad evq;
-    if (!ev_free_.empty()) {
-        evq = ev_free_.back();
-        ev_free_.pop_back();
-    } else {
-        HIPTRY(hipEventCreate(&evq.k0));
-        HIPTRY(hipEventCreate(&evq.k1));
-        HIPTRY(hipEventCreate(&evq.p0));
-        HIPTRY(hipEventCreate(&evq.p1));
-        HIPTRY(hipEventCreate(&evq.f0));
-        HIPTRY(hipEventCreate(&evq.f1));
-    }
-    evq.step_id = step_id;
-    evq.has_k2 = false;
-    auto host_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    evq.h_enter = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
-    // (two timing events before and three after the bank cost the stream ~15 us per launch -- 2 % of a 0.7 ms step)
-    const bool timed = timing_every_ > 0 && (launch_seq_ % (unsigned)timing_every_) == 0;
-    // ---- preparation stream: this set's device buffers are free once the oscillator bank that last read them (N_SETS
-    //      launches ago) has finished.  (The upload stays on this stream: on one of its own the next launch's scan starts as soon
-    //      as this launch's has finished -- beside the START of a bank, whose workgroups then wait for the slots it holds:
-    //      512 x 512 x 86 0.51 -> 0.59 ms per step, scripts/debug/r04_sync.sh.)
-    QHIP(hipStreamWaitEvent, sp, ev_k1_done_[cur_set_], 0);
-    if (timed) QHIP(hipEventRecord, evq.p0, sp);
-    evq.h_prep = host_ms();
-    // ---- ONE upload: everything the planner produced sits behind the descriptors in the set's pinned arena.
-    // (Twelve separate copies cost the host 0.1 ms of API calls per step, and the small ones went through
-    // blit kernels that cannot start while the oscillator bank fills the register file.)
-    std::vector<int> cp;
-    const int n_cl = (int)copy_latest.size() / 2, n_cq = (int)copy_queued.size() / 2;
-    {
-        // layout: [src...] then [dst...]
-        cp.resize((size_t)2 * (n_cl + n_cq));
-        for (int i = 0; i < n_cl; ++i) { cp[i] = copy_latest[2 * i]; cp[n_cl + n_cq + i] = copy_latest[2 * i + 1]; }
-        for (int i = 0; i < n_cq; ++i) { cp[n_cl + i] = copy_queued[2 * i]; cp[n_cl + n_cq + n_cl + i] = copy_queued[2 * i + 1]; }
-    }
-    // A launch of ONE buffer (the real-time step): the rows of explicit data and the projections whose vectors outlive the buffer are
-    // taken by the combine kernel itself -- every slot filled now is read by exactly one row of this launch -- instead of a scatter and
-    // a projection launch in front of it (kernels_exact.hip: force_combine_kernel).  Any slot that is NOT read exactly once (a force
-    // whose profile is all zero in this buffer leaves its row out) keeps the separate launches.
-    bool fuse_combine = fuse_short_ && nb == 1 && n_frows > 0 && (!stage_slot_.empty() || !proj_.empty());
-    if (fuse_combine) {
-        const int n_ev = (int)(proj_direct_.size() + proj_.size());
-        std::unordered_map<int, std::pair<int, int>> code;      // slot -> (entry, references)
-        for (size_t e = 0; e < proj_.size(); ++e) code[proj_[e].slot] = {-((int)(proj_direct_.size() + e) + 1), 0};
-        for (size_t r = 0; r < stage_slot_.size(); ++r) code[stage_slot_[r]] = {-(n_ev + (int)r + 1), 0};
-        fuse_combine = code.size() == proj_.size() + stage_slot_.size();      // (a slot filled twice in one launch: never, but not fused)
-        for (int si : slot_idx_) {
-            if (si < 0) continue;
-            auto it = code.find(si);
-            if (it != code.end()) ++it->second.second;
-        }
-        for (const auto &kv : code) fuse_combine = fuse_combine && kv.second.second == 1;
-        if (fuse_combine) {
-            for (int &si : slot_idx_) {
-                if (si < 0) continue;
-                auto it = code.find(si);
-                if (it != code.end()) si = it->second.first;
-            }
-            proj_direct_.insert(proj_direct_.end(), proj_.begin(), proj_.end());
-            proj_.clear();
-        }
-    }
-    const int n_proj = (int)proj_.size() + n_stroke_proj_;      // (behind the fusion above, which may have emptied proj_)
-    size_t off = ps.front_bytes;
-    auto place = [&](size_t bytes) { const size_t o = off; off += arena_align(bytes); return o; };
-    // (every table with stroke rows: room for them behind the host's part; stroke_expand_kernel fills it in the device copy)
-    const size_t o_row_ptr = place((row_ptr_.size() + n_srows) * sizeof(int)), o_slot_idx = place((slot_idx_.size() + n_srows) * sizeof(int));
-    const size_t o_row_obj = place((row_obj_.size() + n_srows) * sizeof(int));
-    const size_t o_prow_obj = place((prow_obj_.size() + n_srows) * sizeof(int));
-    const size_t o_pent = place(device_profiles_ ? (prof_entries_.size() + n_srows) * sizeof(ProfEntry) : 0);
-    const size_t o_prow = place(device_profiles_ ? (size_t)n_prof_rows * sizeof(ProfRow) : 0);
-    const size_t o_chain = place(device_profiles_ ? chain_ptr_.size() * sizeof(int) : 0);
-    const size_t o_aruse = place((size_t)n_ar_uses * sizeof(ArUse)), o_arstream = place(ar_streams_.size() * sizeof(ArStream));
-    const size_t o_arseg = place(seg_stream_.size() * sizeof(int));
-    const size_t o_tprof = place(device_profiles_ ? 0 : tprof_.size() * sizeof(float));
-    const size_t o_stage = place(stage_.size() * sizeof(double)), o_stage_slot = place(stage_slot_.size() * sizeof(int));
-    const size_t o_proj = place((size_t)n_proj * sizeof(ProjectEvent)), o_projd = place(proj_direct_.size() * sizeof(ProjectEvent));
-    // the stroke records and the part of the caller's arrays they refer to, as given (the arrays are borrowed only until the step returns)
-    const int s_lo = n_srecs ? stroke_recs_.front().e0 : 0, s_n = n_srecs ? stroke_recs_.back().e0 + stroke_recs_.back().n_ent - s_lo : 0;
-    const size_t o_srec = place((size_t)n_srecs * sizeof(StrokeRec)), o_sstamp = place((size_t)s_n * sizeof(int64_t));
-    const size_t o_svids = place((size_t)s_n * 3 * sizeof(int)), o_scoords = place((size_t)s_n * 3 * sizeof(double));
-    const size_t o_svn = place((size_t)s_n * 3 * sizeof(double)), o_sflags = place(script_.flags ? (size_t)s_n : 0);
-    // the listener events as runs of one object each (the planner lists them object by object): one geometry read per (run, mode)
-    // (events of objects whose modes share one map geometry first: they go to the kernel that locates a position once per event)
-    int n_ffat_sh = 0;
-    if (n_ffat_shared_ > 0 && !ffat_.empty()) {
-        auto mid = std::stable_partition(ffat_.begin(), ffat_.end(), [&](const FfatEvent &e) { return ffat_shared_h_[e.obj] != 0; });
-        n_ffat_sh = (int)(mid - ffat_.begin());
-    }
-    const int n_ffat_gen = (int)ffat_.size() - n_ffat_sh;
-    tot_ffat_shared_events_ += n_ffat_sh;
-    tot_ffat_general_events_ += n_ffat_gen;
-    ffat_runs_.clear();
-    for (size_t i = (size_t)n_ffat_sh; i < ffat_.size(); ++i) {
-        if (ffat_runs_.empty() || ffat_runs_.back().obj != ffat_[i].obj) ffat_runs_.push_back(FfatRun{ffat_[i].obj, (int)i, 0, 0});
-        ffat_runs_.back().count += 1;
-    }
-    const size_t o_ffat = place(ffat_.size() * sizeof(FfatEvent)), o_copy = place(cp.size() * sizeof(int));
-    const size_t o_ffat_runs = place(ffat_runs_.size() * sizeof(FfatRun));
-    HIPTRY(ps.h_arena.ensure_keep(off, ps.front_bytes));
-    plan_desc_ = reinterpret_cast<BufDesc *>(ps.h_arena.p);      // (the arena may have moved)
-    ps.last_bytes = off;
-    unsigned char *ha = ps.h_arena.p;
-    auto put = [&](size_t o, const void *src, size_t bytes) { if (bytes) std::memcpy(ha + o, src, bytes); };
-    put(o_row_ptr, row_ptr_.data(), row_ptr_.size() * sizeof(int));
-    put(o_slot_idx, slot_idx_.data(), slot_idx_.size() * sizeof(int));
-    put(o_row_obj, row_obj_.data(), row_obj_.size() * sizeof(int));
-    put(o_prow_obj, prow_obj_.data(), prow_obj_.size() * sizeof(int));
-    if (device_profiles_) {
-        put(o_pent, prof_entries_.data(), prof_entries_.size() * sizeof(ProfEntry));
-        put(o_prow, prof_rows_.data(), prof_rows_.size() * sizeof(ProfRow));
-        put(o_chain, chain_ptr_.data(), chain_ptr_.size() * sizeof(int));
-        put(o_aruse, ar_uses_.data(), ar_uses_.size() * sizeof(ArUse));
-        put(o_arstream, ar_streams_.data(), ar_streams_.size() * sizeof(ArStream));
-        put(o_arseg, seg_stream_.data(), seg_stream_.size() * sizeof(int));
-        if (k2_rows_launch_) {
-            const size_t ns = std::max<size_t>(1, ar_streams_.size()), nu = std::max<size_t>(1, (size_t)n_ar_uses);
-            const size_t ng = std::max<size_t>(1, seg_stream_.size());
-            GROWTRY(d_ar_snaps_, ns, false, sp);
-            GROWTRY(d_ar_fins_, ns, false, sp);
-            GROWTRY(d_ar_recs_, nu, false, sp);
-            GROWTRY(d_ar_cbuf_, nu * (size_t)b_pad_, false, sp);
-            GROWTRY(d_ar_vnorm_, ng * 2 * K2_SEG, false, sp);
-            GROWTRY(d_ar_vstate_, ng * K2_SEG, false, sp);
-            GROWTRY(d_ar_segcount_, ng, false, sp);
-        }
-        GROWTRY(ps.d_tprof, std::max<size_t>(1, (size_t)n_prows_) * b_pad_, false, sp);
-        GROWTRY(d_arstate_, std::max<size_t>(1, n_ar_states_.load()), true, sp);
-    } else {
-        put(o_tprof, tprof_.data(), tprof_.size() * sizeof(float));
-    }
-    put(o_stage, stage_.data(), stage_.size() * sizeof(double));
-    put(o_stage_slot, stage_slot_.data(), stage_slot_.size() * sizeof(int));
-    put(o_proj, proj_.data(), proj_.size() * sizeof(ProjectEvent));
-    put(o_projd, proj_direct_.data(), proj_direct_.size() * sizeof(ProjectEvent));
-    if (n_srecs) {
-        StrokeRec *hr = reinterpret_cast<StrokeRec *>(ha + o_srec);
-        for (int i = 0; i < n_srecs; ++i) { hr[i] = stroke_recs_[(size_t)i]; hr[i].e0 -= s_lo; }
-        put(o_sstamp, script_.stamps + s_lo, (size_t)s_n * sizeof(int64_t));
-        put(o_svids, script_.vids + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(int));
-        put(o_scoords, script_.coords + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(double));
-        put(o_svn, script_.vn + 3 * (size_t)s_lo, (size_t)s_n * 3 * sizeof(double));
-        if (script_.flags) put(o_sflags, script_.flags + s_lo, (size_t)s_n);
-    }
-    put(o_ffat, ffat_.data(), ffat_.size() * sizeof(FfatEvent));
-    put(o_ffat_runs, ffat_runs_.data(), ffat_runs_.size() * sizeof(FfatRun));
-    put(o_copy, cp.data(), cp.size() * sizeof(int));
-    GROWTRY(ps.d_arena, off, false, sp);
-    QHIP(hipMemcpyAsync, ps.d_arena.p, ha, off, hipMemcpyHostToDevice, sp);
-    QHIP(hipEventRecord, ev_set_[cur_set_], sp);          // this set's pinned arena is reusable
-    // the start gate: this launch's preparation kernels behind the START of the previous launch's bank (engine.h).  By policy
-    // for LONG launches only: there the gate's few microseconds are nothing, and what it prevents is expensive -- a scan of 860
-    // buffers that the preparation stream runs TWO launches ahead trails the bank it was squeezed beside by 0.2 ms, holds LDS
-    // while the next bank starts, and that bank's left-over workgroups wait a whole workgroup's length (512 x 512 x 860: every
-    // other launch 9 instead of 4.6 ms in one run of four).  Gated, a scan is never more than one launch ahead, and the bank
-    // that needs it waits for it.
-    // (stream_sync = 4, round 5: the gate as a wait of the SUBMITTING thread on a word of pinned host memory the previous bank's
-    //  first workgroup writes.  Built because hipStreamWaitValue64 runs on this stack as a kernel that waits -- `__amd_rocclr_streamOpsWait`
-    //  sits 1.1 of a 1.28 ms bank until workgroups retire, scripts/debug/r05_timeline_share.sh -- and was suspected behind the share's
-    //  outlier runs; those came from the planner's helper threads (PlanPool::run), both forms show them alike, and the host form
-    //  costs the host its second launch of run-ahead: an option, not the policy.)
-    const bool gate_now = !one_stream && last_bank_seq_ > 0 && (desc_.stream_sync == 3 || desc_.stream_sync == 4 || nb >= 256);
-    host_gate_used_ = false;
-    if (gate_now && host_start_ && desc_.stream_sync == 4) {
-        const auto tg0 = std::chrono::steady_clock::now();
-        volatile unsigned long long *w = host_start_;
-        while (*w < last_bank_seq_) {
-            std::this_thread::yield();
-            // (fail-safe: a bank that never starts -- a device fault -- must not hang the caller; the launch then goes ungated)
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count() > 2.0) {
-                ++gate_timeouts_;                         // (pbso_engine_info::total_gate_timeouts)
-                break;
-            }
-        }
-        host_gate_used_ = true;
-    } else if (gate_now && start_gate_) {
-        QHIP(hipStreamWaitValue64, sp, sig_start_, last_bank_seq_, hipStreamWaitValueGte, ~0ull);
-    }
-    evq.h_copy = host_ms();
-    const auto tsub1 = std::chrono::steady_clock::now();
-    unsigned char *da = ps.d_arena.p;
-    if (n_srecs) {
-        // stroke records -> descriptors, events, profile rows: behind the upload (it overwrites the eligible objects' default rows in
-        // the device copy), in front of everything that reads the plan
-        StrokeTables st;
-        std::memset(&st, 0, sizeof(st));
-        st.recs = reinterpret_cast<const StrokeRec *>(da + o_srec);
-        st.stamps = reinterpret_cast<const int64_t *>(da + o_sstamp);
-        st.vids = reinterpret_cast<const int32_t *>(da + o_svids);
-        st.coords = reinterpret_cast<const double *>(da + o_scoords);
-        st.vn = reinterpret_cast<const double *>(da + o_svn);
-        st.flags = script_.flags ? da + o_sflags : nullptr;
-        st.buffers_done = buffers_done_;
-        st.nb = nb;
-        st.tile_mask = n_tiles_ >= 32 ? 0xFFFFFFFFu : ((1u << n_tiles_) - 1u);
-        st.desc = reinterpret_cast<BufDesc *>(da);
-        st.row_ptr = reinterpret_cast<int32_t *>(da + o_row_ptr);
-        st.slot_idx = reinterpret_cast<int32_t *>(da + o_slot_idx);
-        st.row_obj = reinterpret_cast<int32_t *>(da + o_row_obj);
-        st.prow_obj = reinterpret_cast<int32_t *>(da + o_prow_obj);
-        st.prof_rows = reinterpret_cast<ProfRow *>(da + o_prow);
-        st.prof_entries = reinterpret_cast<ProfEntry *>(da + o_pent);
-        st.ar_uses = k2_rows_launch_ ? reinterpret_cast<ArUse *>(da + o_aruse) : nullptr;
-        st.proj = reinterpret_cast<ProjectEvent *>(da + o_proj);
-        st.slots = d_slots_.p;
-        st.frow_base = n_frows - n_srows;
-        st.prow_base = n_prows_ - n_srows;
-        st.sidx_base = (int)slot_idx_.size();
-        st.entry_base = (int)prof_entries_.size();
-        st.prof_row_base = (int)prof_rows_.size();
-        st.use_base = (int)ar_uses_.size();
-        st.proj_base = (int)proj_.size();
-        st.m_pad = m_pad_;
-        if (host_profile_ && stroke_ev_[cur_set_][0]) QHIP(hipEventRecord, stroke_ev_[cur_set_][0], sp);
-        QLAUNCH(launch_stroke_expand, st, n_srecs, sp);
-        if (host_profile_ && stroke_ev_[cur_set_][0]) { QHIP(hipEventRecord, stroke_ev_[cur_set_][1], sp); stroke_ev_live_[cur_set_] = true; }
-        tot_stroke_launches_ += 1;
-    }
-    const BufDesc *d_desc = reinterpret_cast<const BufDesc *>(da);
-    const int *d_xfer_init = reinterpret_cast<const int *>(da + ps.off_xfer_init);
-    const int *d_row_ptr = reinterpret_cast<const int *>(da + o_row_ptr), *d_slot_idx = reinterpret_cast<const int *>(da + o_slot_idx);
-    const int *d_row_obj = reinterpret_cast<const int *>(da + o_row_obj), *d_chain = reinterpret_cast<const int *>(da + o_chain);
-    const ProfEntry *d_pent = reinterpret_cast<const ProfEntry *>(da + o_pent);
-    const ProfRow *d_prow = reinterpret_cast<const ProfRow *>(da + o_prow);
-    const float *d_tprof = device_profiles_ ? ps.d_tprof.p : reinterpret_cast<const float *>(da + o_tprof);
-    const double *d_stage = reinterpret_cast<const double *>(da + o_stage);
-    const int *d_stage_slot = reinterpret_cast<const int *>(da + o_stage_slot), *d_copy = reinterpret_cast<const int *>(da + o_copy);
-    const ProjectEvent *d_proj = reinterpret_cast<const ProjectEvent *>(da + o_proj), *d_projd = reinterpret_cast<const ProjectEvent *>(da + o_projd);
-    const FfatEvent *d_ffat = reinterpret_cast<const FfatEvent *>(da + o_ffat);
-
-    const bool dense_heavy = is_block() && dense_to_k1_ && (long long)n_prows_ * 2 > (long long)N * nb;
-    IirParams kp;
-    kp.ca = d_ca_.p; kp.cb = d_cb_.p; kp.sq = d_sq_.p; kp.sd = d_sd_.p; kp.ss = d_ss_.p;
-    kp.desc = d_desc;
-    kp.grows = grows.p;
-    kp.g32 = d_g32_.p;
-    kp.g32_off = d_g32_off_.p;
-    kp.tprof = d_tprof;
-    kp.xfer_rows = d_xfer_.p;
-    kp.xfer_init = d_xfer_init;
-    kp.audio = audio + (size_t)b0 * B_;
-    kp.qnorm = (qn || n_dump_ > 0) ? d_qnorm_.p : nullptr;
-    kp.xdump = n_dump_ > 0 ? d_xdump_.p : nullptr;
-    kp.xscale = d_xscale_.p;
-    kp.dump_row = d_dump_row_.p;
-    kp.qn_nb = nb_total;
-    kp.qn_b0 = b0;
-    kp.gq = d_gq_.p;
-    kp.gq_plane = (long long)N * m_pad_;
-    kp.census = nullptr;
-    if (census_) {
-        size_t rows = (size_t)std::max(n_teams_, use_split() ? n_ts_teams_ : 0);
-        if (tc_ok_) for (const TcSet &ts : tc_) rows = std::max(rows, (size_t)ts.n_teams * nb);
-        GROWTRY(d_census_, rows * CENSUS_WORDS, false, sk);
-        kp.census = d_census_.p;
-    }
-    kp.nb = nb; kp.n_tiles = n_tiles_; kp.m_pad = m_pad_; kp.b_pad = b_pad_;
-    kp.audio_stride = (long long)nb_total * B_;
-    // the per-CU progress feedback only pays when several teams compete for every SIMD
-    kp.rotate_prio = (rotate_prio_ == 2 && total_team_waves_ < 12LL * n_cus_) ? 1 : rotate_prio_;
-    kp.board = d_board_.p;
-    kp.launch_seq = ++launch_seq_;
-    kp.start_flag = (host_start_ && desc_.stream_sync == 4) ? host_start_dev_ : (start_gate_ ? sig_start_ : nullptr);
-    kp.start_seq = ++bank_seq_;
-    kp.pc = d_pc_.p;
-    kp.wtab = d_wtab_.p;
-    kp.frames = B_;
-    kp.ftab = ftab_forced_ ? d_ftab_.p : nullptr;
-    kp.forced_block = (forced_block_ && n_prows_ > 0) ? 1 : 0;      // (the build with the forced block path only when a buffer needs it)
-    // K2 -> time-profile rows ; K3 / scatter -> data slots ; K4 -> transfer rows ; combine -> g rows
-    // Round 5: a launch with many dense-profile rows FORKS its preparation.  The force profiles (variates -> zero-state chains ->
-    // rows) and the dense increments that need them are one dependent chain, projection -> combine another, and nothing connects
-    // the two before the scan; in one stream they ran one after the other BESIDE the previous bank -- 8 x 4096 x 86 sustained
-    // scraping with qnorm rows: 31 + 54 + 73 (profiles) + 29 + 15 (project, combine) + 78 (increments) = 280 us beside a bank of
-    // 283, then the scan: the preparation, not the bank, set the step (scripts/debug/r05_timeline_c5.sh).  Forked, projection +
-    // FFAT + combine run on aux_stream_ behind the upload and join the preparation stream in front of the scan (or of the
-    // hand-over to the bank): every later reader is ordered behind prep_stream_ as before.
-    const bool split_prep = !one_stream && aux_stream_ && prep_split_ > 0 && device_profiles_ && n_prows_ > 0 &&
-                            (prep_split_ == 2 || n_prows_ >= 64) && (n_frows > 0 || !proj_.empty() || !ffat_.empty() || !stage_slot_.empty());
-    hipStream_t sa = split_prep ? aux_stream_ : sp;
-    if (split_prep) {
-        tot_prep_splits_ += 1;
-        QHIP(hipEventRecord, ev_aux_fork_[cur_set_], sp);         // (behind the upload and, for gated launches, the start gate)
-        QHIP(hipStreamWaitEvent, sa, ev_aux_fork_[cur_set_], 0);
-    }
-    if (device_profiles_ && timed && n_chains > 0) { QHIP(hipEventRecord, evq.f0, sp); evq.has_k2 = true; }
-    // (round 6, second half) a one-buffer launch whose profile rows go through the fused kernel and whose combine takes its rows itself:
-    // both in ONE launch -- they touch different arrays (kernels_exact.hip, force_rows_combine_kernel)
-    const bool rows_and_combine = device_profiles_ && k2_rows_launch_ && fuse_combine && sa == sp && !prof_rows_.empty() && n_frows > 0 &&
-                                  fuse_short_ && !ar_uses_.empty() && ar_uses_.size() == ar_streams_.size();
-    if (rows_and_combine)
-        QLAUNCH(launch_force_rows_combine, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse),
-                                            reinterpret_cast<const ArStream *>(da + o_arstream), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p,
-                                            d_ar_vnorm_.p, d_ar_vstate_.p, d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p,
-                                            ps.d_tprof.p, track_device_pool(), track_device_table(), B_, b_pad_, b_pad_, d_row_ptr, d_slot_idx,
-                                            d_row_obj, n_frows, d_slots_.p, d_c3_.p,
-                                            grows.p, d_projd, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, m_pad_, (int)proj_direct_.size(),
-                                            d_stage, d_stage_slot, sp);
-    else if (device_profiles_ && k2_rows_launch_)
-        QLAUNCH(launch_force_rows, d_prow, n_prof_rows, d_pent, reinterpret_cast<const ArUse *>(da + o_aruse), n_ar_uses,
-                                    reinterpret_cast<const ArStream *>(da + o_arstream), reinterpret_cast<const int *>(da + o_arseg),
-                                    (int)seg_stream_.size(), ar_max_segs_, d_arstate_.p, d_ar_snaps_.p, d_ar_vnorm_.p, d_ar_vstate_.p,
-                                    d_ar_segcount_.p, d_ar_cbuf_.p, d_ar_recs_.p, d_ar_fins_.p, ps.d_tprof.p, track_device_pool(),
-                                    track_device_table(), B_, b_pad_, b_pad_,
-                                    /* every AR force adds its samples once (a launch of one buffer): one launch instead of three */
-                                    fuse_short_ && n_ar_uses > 0 && (size_t)n_ar_uses == ar_streams_.size(), sp);
-    else if (device_profiles_)
-        QLAUNCH(launch_force_profiles, d_chain, n_chains, d_prow, d_pent, d_arstate_.p, ps.d_tprof.p, track_device_pool(), track_device_table(),
-                                        B_, b_pad_, ar_serial_ ? 1 : 0, k2_prio_, sp);
-    if (evq.has_k2) QHIP(hipEventRecord, evq.f1, sp);
-    if (!fuse_combine) QLAUNCH(launch_scatter_rows, d_stage, d_stage_slot, (int)stage_slot_.size(), d_slots_.p, m_pad_, sa);
-    QLAUNCH(launch_modal_project, d_proj, n_proj, d_shapes_.p, d_shape_off_.p, d_n_modes_.p, d_slots_.p, m_pad_, sa);
-    // (a few events: one thread per (event, mode); listener paths -- many events per object -- by runs)
-    if (n_ffat_sh > 0)
-        QLAUNCH(launch_ffat_lookup_shared, d_ffat, n_ffat_sh, d_ffat_shared_.p, d_geom_.p, d_geom_off_.p, d_n_modes_.p, d_ffat_k_.p,
-                                            d_ffat_valid_.p, d_psi_t_.p, d_xfer_.p, m_pad_, sa);
-    if ((size_t)n_ffat_gen >= 4 * ffat_runs_.size() && !ffat_runs_.empty())
-        QLAUNCH(launch_ffat_lookup_runs, d_ffat, reinterpret_cast<const FfatRun *>(da + o_ffat_runs), (int)ffat_runs_.size(), d_geom_.p,
-                                          d_geom_off_.p, d_n_modes_.p, d_psi_.p, d_xfer_.p, m_pad_, sa);
-    else
-        QLAUNCH(launch_ffat_lookup, d_ffat + n_ffat_sh, n_ffat_gen, d_geom_.p, d_geom_off_.p, d_n_modes_.p, d_psi_.p, d_xfer_.p, m_pad_, sa);
-    // (the combine stays on the preparation stream even when the bank fills the register file: its workgroups
-    //  move in as the bank's retire, so most of it is done when the last one leaves -- queued behind the bank in
-    //  the bank's own stream it would start only then: 0.785 instead of 0.735 ms per step at 1024 x 512)
-    if (!rows_and_combine)
-        QLAUNCH(launch_force_combine, d_row_ptr, d_slot_idx, d_row_obj, n_frows, d_slots_.p, d_c3_.p, grows.p, d_projd, d_shapes_.p,
-                                       d_shape_off_.p, d_n_modes_.p, m_pad_, (int)proj_direct_.size(), d_stage, d_stage_slot, sa);
-    if (split_prep) QHIP(hipEventRecord, ev_aux_join_[cur_set_], sa);
-    if (split_prep && !tc_launch) QHIP(hipStreamWaitEvent, sp, ev_aux_join_[cur_set_], 0);
-    if (tc_launch) {
-        // The scan hands the state from launch to launch by itself (the chunked bank launches never write it), so it runs HERE, on
-        // the preparation stream, beside the previous launch's oscillator bank -- behind a launch of another kind it waits for
-        // that launch's bank, which wrote the state it starts from.
-        const int n_chunks = (nb + tc_cb - 1) / tc_cb;
-        GROWTRY(d_xs_[cur_set_], (size_t)N * n_chunks * m_pad_ * 2, false, sp);
-        GROWTRY(d_xtrow_[cur_set_], (size_t)N * n_chunks, false, sp);
-        // dense-profile buffers (Gaussian / AR, forces.h:92-128): what each leaves in the state per unit gain, all of them at once
-        const float *vinc = nullptr;
-        if (n_prows_ > 0) {
-            GROWTRY(d_vinc_[cur_set_], (size_t)n_prows_ * m_pad_ * 2, false, sp);
-            QLAUNCH(launch_dense_increments, d_pc_.p, d_ftab_.p, (long long)N * m_pad_, d_tprof, reinterpret_cast<const int *>(da + o_prow_obj),
-                                              d_n_modes_.p, n_prows_, m_pad_, b_pad_, B_, d_vinc_[cur_set_].p, sp);
-            vinc = d_vinc_[cur_set_].p;
-            tot_tc_dense_launches_ += 1;
-        }
-        if (!last_launch_tc_ && last_set_ >= 0) QHIP(hipStreamWaitEvent, sp, ev_k1_done_[last_set_], 0);
-        if (split_prep) QHIP(hipStreamWaitEvent, sp, ev_aux_join_[cur_set_], 0);      // (the increments above did not need the gains; the scan does)
-        // Cut along the time axis itself -- one wave per chunk (kernels_scan.hip, SEG) -- in two cases.  (a) The whole scan is a
-        // handful of waves: it halves the latency of a scan that has the device to itself (1 x 512 x 86: 11.3 -> 5.7 us).  (b) LONG
-        // chunks of a scene whose serial scan is at most two waves per SIMD: that scan can only start as the previous bank's
-        // workgroups retire (the bank holds every register), so the waves placed last start when the bank ends and what the next
-        // bank waits for is ONE WAVE'S walk over all buffers of the launch -- 82 us for 860 buffers; cut into the bank's own
-        // chunks a wave walks 108 and the whole scan is 45 us of a throughput-bound kernel, most of it beside the bank's tail:
-        // 128 x 512 x 860 1.31 -> 1.27 ms per step, 256 x 512 x 860 2.45 -> 2.42 (scripts/debug/r05_scan_seg2.sh).  NOT for
-        // four serial waves per SIMD (512 x 512: the serial scan is throughput-bound already and does less work: 4.79 against
-        // 4.87 ms) and not for short chunks (86-buffer steps, 11 buffers per chunk: 0.156 against 0.160 ms -- eight times the
-        // waves for one batch each).  (c) A DENSE scan (every buffer a hit with a row of increments: 64 hits per serial batch,
-        // sixteen in flight) of at most two waves per CU: 8 x 4096 x 86 sustained scraping with qnorm rows 0.320 -> 0.312 ms per
-        // step (scripts/debug/r05_seg_short.sh).  One buffer per chunk keeps the serial scan, whose arithmetic does not depend
-        // on where a step is cut.
-        const bool seg_fits = n_chunks >= 2 && n_chunks <= SCAN_SEG_MAX;
-        const long long scan_waves = (long long)N * (m_pad_ / 64);
-        const bool seg = seg_fits && desc_.scan_kernel != 1 &&
-                         (desc_.scan_kernel == 2 || (tc_cb > 1 && scan_waves * n_chunks <= 2LL * n_cus_) ||
-                          (tc_cb >= 32 && scan_waves <= 8LL * n_cus_) || (tc_cb > 1 && vinc && scan_waves <= 2LL * n_cus_));
-        if (seg) tot_seg_scans_ += 1;
-        QLAUNCH(launch_iir_scan, kp, N, d_scan_.p, tc_cb, n_chunks, d_xs_[cur_set_].p, d_xtrow_[cur_set_].p, direct_hits_, vinc, seg, sp);
-    }
-    // ---- compute stream: the bank after its preparation (and, stream order, after the previous bank)
-    if (one_stream) {
-        tot_one_stream_launches_ += 1;
-    } else if (sync_values_ && (desc_.stream_sync == 2 || nb < 256)) {
-        // (round 6: by policy for launches of fewer than 256 buffers -- a step of 86 buffers: 64 x 256 with a listener move per buffer
-        //  0.0765 -> 0.0717 ms, 16 / 128 / 256 / 512 x 512 impulses 4 / 2.7 / 1.7 / 1.5 % per step, 64 x 512 and 1 x 512 unchanged,
-        //  profiles/r06_value_handover.txt; long launches keep the event: nothing to gain there, and their numbers stand as measured)
-        QLAUNCH(launch_signal_value, sig_prep_, ++prep_seq_, sp);
-        QHIP(hipStreamWaitValue64, sk, sig_prep_, prep_seq_, hipStreamWaitValueGte, ~0ull);
-    } else {
-        QHIP(hipEventRecord, ev_prep_done_[cur_set_], sp);
-        QHIP(hipStreamWaitEvent, sk, ev_prep_done_[cur_set_], 0);
-    }
-    const auto tsub2 = std::chrono::steady_clock::now();
-    if (timed) QHIP(hipEventRecord, evq.k0, sk);
-    evq.h_bank = host_ms();
-    kp.audio_parts = d_audio_parts_.p ? d_audio_parts_.p + (size_t)b0 * B_ : nullptr;
-    // Side by side only while everything is resident at once (largest teams first, on the engine's
-    // stream); an engine that needs several rounds of workgroups runs its classes one after the other
-    // (512 x 512 + 4096 x 64: 3.1 ms in sequence, 3.7 ms side by side -- teams of different size fragment
-    // the CUs' LDS and wave slots).
-    // Block form: a launch in which most (object, buffer) pairs carry a dense force profile -- sustained
-    // scraping, forces.h:107-128 -- has nothing for the matrix pipe to do (every sample is forced) and runs on the
-    // per-sample kernel K1, whose inner loop is built for exactly that; state layout, teams and scaled-state
-    // rules are shared, so the two kernels hand over at any launch boundary.  (Audio then is bit-identical
-    // across different cuts of a step only while both cuts pick the same kernel; always within tolerance.)
-    // PBSO_DENSE_LAUNCHES=block keeps every launch on the block kernel (bit-identical audio for any cut of a step).
-    // The pipeline kernel of under-filled engines (K1p) takes the launch -- also one whose (object, buffer)
-    // pairs mostly carry a dense force profile (sustained scraping) when the profiles come from K2's row-parallel form
-    // (8 x 4096 x 86: 0.30 ms against K1b's 0.43 without qnorm rows, 0.48 against 0.74 with).  Beside K2's CHAIN form -- then
-    // the step's critical chain, which a wave on every SIMD slows 2.7 x (1.28 ms against 0.48 for 8 chains of 86 rows beside
-    // K1b's 512 waves) -- K1b's forced block path keeps those launches (state and teams hand over at any launch boundary).
-    // Without the F table of the forced block path (PBSO_FORCED_BLOCK=0) and without qnorm rows they go to K1b as well.
-    const bool dense_majority = (long long)n_prows_ * 2 > (long long)N * nb;
-    const bool split_dense_ok = k2_rows_launch_ && (desc_.qnorm_mode != PBSO_QNORM_OFF || ftab_forced_);
-    const bool split_launch = !tc_launch && use_split() && (split_always_ || !dense_majority || split_dense_ok);      // (PBSO_SPLIT=2: always)
-    (tc_launch || split_launch || !(dense_heavy || !is_block()) ? tot_block_launches_ : tot_sample_launches_) += 1;
-    if (split_launch) tot_split_launches_ += 1;
-    if (tc_launch) {
-        tot_tc_launches_ += 1;
-        last_tc_shape_ = tc_[tc_set].R;
-        last_tc_cb_ = tc_cb;
-        last_tc_teams_ = tc_[tc_set].n_teams;
-    }
-    if (n_dump_ > 0) {
-        // the mix needs block states: a launch on the per-sample kernel leaves none, a dense-profile buffer neither
-        for (int i = 0; i < N; ++i) {
-            if (dump_row_[i] < 0) continue;
-            if (!tc_launch && (dense_heavy || !is_block())) { dump_valid_[i] = 0; continue; }
-            for (int b = 0; b < nb; ++b)
-                if (!(plan_desc_[(size_t)i * nb + b].flags & DESC_DIRECT) && plan_desc_[(size_t)i * nb + b].prow >= 0) { dump_valid_[i] = 0; break; }
-        }
-    }
-    bool used[N_CLASS_STREAMS] = {false, false, false};
-    if (tc_launch) {
-        TcSet &ts = tc_[tc_set];
-        kp.tc_cb = tc_cb;
-        kp.tc_xs = d_xs_[cur_set_].p;
-        kp.tc_xtrow = d_xtrow_[cur_set_].p;
-        kp.census_stride = ts.n_teams;
-        // The priority rotation (kernels_block.hip) assumes the teams of a CU walk their buffers in step.  A launch of several
-        // ROUNDS of workgroups does not: a team that arrives when another retires starts at its own chunk's first buffer, two
-        // teams of a CU then hold the same priority and the oldest-first arbitration is back -- 1024 x 512 forced into two
-        // chunks: 1.33 ms against 1.07 without the rotation; 700 x 512: 0.751 against 0.742 (scripts/debug/r04_tcrounds.py).
-        // (A phase taken from the wall clock instead of the team's buffer count does not help: 0.752 ms at 700 x 512.)
-        kp.rotate_prio = (rotate_prio_ && ts.waves * (long long)((nb + tc_cb - 1) / tc_cb) <= 8LL * n_cus_) ? 1 : 0;
-        for (const SizeClass &c : ts.classes) {
-            kp.teams = ts.d_teams.p + c.first;
-            QLAUNCH(iir_block::launch_iir_block, kp, c.count, ts.R, c.W, desc_.qnorm_mode, form_ == PBSO_FORM_BLOCK_BF16 ? 1 : 0, sk);
-        }
-    }
-    if (split_launch) {
-        kp.teams = d_ts_teams_.p;
-        {
-            // two consumers (one group each) also where that puts a second wave on some SIMDs: 8 x 4096 scraping -- 512 teams, 1536
-            // waves -- runs 3120 x against 2800 with one consumer (no qnorm rows) and 1700 x against 1590 (with them)
-            int nc = 2;
-            // qnorm rows of a mostly-dense launch: the consumers re-step every sample for the sums and are the long stage -- a third
-            // consumer wave that only steps (half of the chains) when that still leaves at most two waves per SIMD
-            if (dense_majority && desc_.qnorm_mode != PBSO_QNORM_OFF && ftab_forced_ && 4LL * n_ts_teams_ <= 8LL * n_cus_) nc = 3;
-            // round 5: a mostly-dense launch as teams of FIVE -- the block increments F . T_n come from two waves of their own, a buffer
-            // ahead of the producer, which is left with the 32 coarse steps (kernels_pipe.hip, iir_pipe5_kernel)
-            if (dense_majority && ftab_forced_ && desc_.qnorm_mode == PBSO_QNORM_OFF) nc = 4;
-            if (desc_.pipe_consumers > 0) nc = desc_.pipe_consumers;
-            QLAUNCH(iir_pipe::launch_iir_pipe, kp, n_ts_teams_, nc, desc_.qnorm_mode, sk);
-        }
-    }
-    const bool fork = !tc_launch && !split_launch && classes_.size() > 1 && ev_fork_ && total_team_waves_ <= 16LL * n_cus_;
-    if (fork) QHIP(hipEventRecord, ev_fork_, sk);
-    for (size_t ci = 0; ci < (tc_launch || split_launch ? 0 : classes_.size()); ++ci) {
-        const SizeClass &c = classes_[ci];
-        hipStream_t s = sk;
-        if (fork && ci > 0) {
-            const int j = (int)((ci - 1) % N_CLASS_STREAMS);
-            s = class_stream_[j];
-            if (!used[j]) {
-                QHIP(hipStreamWaitEvent, s, ev_fork_, 0);
-                used[j] = true;
-            }
-        }
-        kp.teams = d_teams_.p + c.first;
-        if (is_block() && !dense_heavy)
-            QLAUNCH(iir_block::launch_iir_block, kp, c.count, R_, c.W, desc_.qnorm_mode, form_ == PBSO_FORM_BLOCK_BF16 ? 1 : 0, s);
-        else
-            QLAUNCH(iir_scalar::launch_iir_bank, kp, c.count, R_, c.W, form_ == PBSO_FORM_DIRECT ? 1 : 0, desc_.qnorm_mode, s);
-    }
-    for (int j = 0; j < N_CLASS_STREAMS; ++j) {
-        if (!used[j]) continue;
-        QHIP(hipEventRecord, ev_join_[j], class_stream_[j]);
-        QHIP(hipStreamWaitEvent, sk, ev_join_[j], 0);
-    }
-    // objects stepped by several teams: the teams' partial sums of this launch's buffers, added in team order
-    // ... and _latest_transfer = trans (modal_solver.h:251) in the same launch; then re-park a still-queued transfer
-    QLAUNCH(launch_sum_parts_copy_rows, tc_launch ? tc_[tc_set].d_split.p : split_launch ? d_ts_split_.p : d_split_.p,
-                                         tc_launch ? tc_[tc_set].n_split : split_launch ? n_ts_split_ : n_split_, kp.audio_parts,
-                                         audio + (size_t)b0 * B_, (long long)nb_total * B_, (long long)nb * B_, d_copy, d_copy + (n_cl + n_cq), n_cl,
-                                         d_xfer_.p, m_pad_, sk);
-    if (timed) QHIP(hipEventRecord, evq.k1, sk);
-    QLAUNCH(launch_copy_rows, d_copy + n_cl, d_copy + (n_cl + n_cq) + n_cl, n_cq, d_xfer_.p, m_pad_, sk);
-    if (timed) QHIP(hipEventRecord, evq.p1, sk);
-    evq.h_done = host_ms();
-    QHIP(hipEventRecord, ev_k1_done_[cur_set_], sk);
-    if (defer) {
-        evq.batch = submit_->pushed() + 1;
-        set_batch_[cur_set_] = submit_->push(std::move(ops));     // (from here on the worker makes the calls; the caller goes on to plan)
-    }
-    if (timed) ev_pending_.push_back(evq);
-    else ev_free_.push_back(evq);
-    buffers_done_ += nb;
-    last_launch_tc_ = tc_launch;
-    last_one_stream_ = one_stream;
-    last_bank_seq_ = kp.start_seq;
-    last_set_ = cur_set_;
-    cur_set_ = (cur_set_ + 1) % N_SETS;
-    hprof_[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - last_plan_ms_;
-    hprof_[6] += std::chrono::duration<double, std::milli>(tsub1 - tsub0).count();
-    hprof_[7] += std::chrono::duration<double, std::milli>(tsub2 - tsub1).count();
-    hprof_[8] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tsub2).count();
-    hprof_[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-    return PBSO_OK;
-}
-
-// the second submitting thread has made every recorded call (NOT a device synchronisation); a call that failed there surfaces here
-int Engine::drain_submit() {
-    if (!submit_) return PBSO_OK;
-    submit_->drain();
-    std::string why;
-    if (submit_->error(&why)) {
-        failed_ = true;
-        failed_why_ = why;
-        return fail(PBSO_ERR_HIP, "a launch failed on the submitting thread: " + why);
-    }
-    return PBSO_OK;
-}
-
 int Engine::sync() {
     {
         int drc = drain_submit();
@@ -3441,63 +1967,6 @@ int Engine::mix_listeners(int obj, const double *pos, int n_listeners, float *ou
     rows.release();
     dout.release();
     return rc;
-}
-
-// Host delivery (the reference's consumer is a host queue of SoundMessages, modal_solver.h:79-82, 346-363): a step whose audio
-// of ALL objects lands in caller memory.  Pinned host memory (pbso_host_alloc, hipHostMalloc, hipHostRegister) is mapped into
-// the device's address space: the oscillator bank writes its samples STRAIGHT into it over PCIe -- every sample is stored
-// exactly once, coalesced -- so delivery needs no second pass and the step runs at the link's rate (1024 x 512 x 86: 3.5 ms per
-// step against 3.2 ms for the bare copy of the same 181 MB; scripts/debug/r04_d2h.py).  What was tried first -- the bank into
-// device memory, then hipMemcpyAsync on a copy stream beside the next step's bank -- does NOT overlap on this stack: the runtime
-// runs the device-to-host copy as a blit KERNEL, which finds no free registers while the bank's two 256-register waves per SIMD
-// are resident (4.35 ms per step waited one by one, 4.65 ms "pipelined").  That staged path remains for pageable memory.
-int Engine::step_to_host(int nb, float *host_out, size_t n) {
-    HIPTRY(hipSetDevice(desc_.device));
-    if (!finalized_) return fail(PBSO_ERR_STATE, "step before finalize");
-    const size_t total = (size_t)objs_.size() * (size_t)std::max(nb, 0) * B_;
-    if (!host_out || nb <= 0 || n != total) return fail(PBSO_ERR_INVALID, "step_to_host arguments (n_floats = n_objects * n_buffers * frames_per_buffer)");
-    if (!copy_stream_) {
-        {
-            // (highest priority: should the runtime run the copy as a blit kernel, its workgroups take the CUs the retiring
-            //  bank frees before the next bank's do)
-            int least = 0, greatest = 0;
-            HIPTRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPTRY(hipStreamCreateWithPriority(&copy_stream_, hipStreamNonBlocking, greatest));
-        }
-        for (int i = 0; i < 2; ++i) {
-            HIPTRY(hipEventCreateWithFlags(&ev_host_bank_[i], hipEventDisableTiming));
-            HIPTRY(hipEventCreateWithFlags(&ev_host_copy_[i], hipEventDisableTiming));
-        }
-    }
-    const int slot = host_slot_;
-    {
-        hipPointerAttribute_t attr;
-        std::memset(&attr, 0, sizeof(attr));
-        if (hipPointerGetAttributes(&attr, host_out) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) {
-            int rc = step(nb, attr.devicePointer);
-            if (rc != PBSO_OK) return rc;
-            host_step_ = tot_steps_;
-            if ((rc = drain_submit()) != PBSO_OK) return rc;          // (the event below goes behind the step's launches)
-            HIPTRY(hipEventRecord(ev_host_copy_[slot], stream_));      // "delivered" = the bank (and what follows it) has finished
-            host_last_ = slot;
-            host_slot_ ^= 1;
-            return PBSO_OK;
-        }
-        (void)hipGetLastError();                         // (a pageable pointer is not an error here)
-    }
-    HIPTRY(d_audio_host_[slot].ensure(total, false, stream_));
-    HIPTRY(hipStreamWaitEvent(stream_, ev_host_copy_[slot], 0));          // the copy that last read this buffer is done
-    int rc = step(nb, d_audio_host_[slot].p);
-    if (rc != PBSO_OK) return rc;
-    host_step_ = tot_steps_;
-    if ((rc = drain_submit()) != PBSO_OK) return rc;
-    HIPTRY(hipEventRecord(ev_host_bank_[slot], stream_));
-    HIPTRY(hipStreamWaitEvent(copy_stream_, ev_host_bank_[slot], 0));
-    HIPTRY(hipMemcpyAsync(host_out, d_audio_host_[slot].p, total * sizeof(float), hipMemcpyDeviceToHost, copy_stream_));
-    HIPTRY(hipEventRecord(ev_host_copy_[slot], copy_stream_));
-    host_last_ = slot;
-    host_slot_ ^= 1;
-    return PBSO_OK;
 }
 
 int Engine::host_wait() {

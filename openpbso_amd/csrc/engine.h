@@ -20,6 +20,8 @@
 
 #include "../../include/openpbso_amd.h"
 #include "kernels.h"
+#include "engine_tables.h"
+#include "launch_policy.h"
 
 namespace pbso {
 class SubmitQueue;       // submit_queue.h
@@ -36,6 +38,12 @@ struct BusWords;         // bus_clock.h
     do {                                                               \
         hipError_t _e = (expr);                                        \
         if (_e != hipSuccess) return hip_fail(_e, #expr);              \
+    } while (0)
+// ... and a failed kernel launch (the launch_* functions of kernels.h return hipError_t as int)
+#define LAUNCHTRY(expr)                                                \
+    do {                                                               \
+        int _e = (expr);                                               \
+        if (_e != 0) return hip_fail((hipError_t)_e, #expr);           \
     } while (0)
 
 // ---- growable device / pinned-host buffers ---------------------------------
@@ -305,6 +313,27 @@ public:
 private:
     int fail(int code, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
+    // finalize's stages (engine_finalize.cpp): what engine_tables.h builds, uploaded
+    int finalize_teams(const std::vector<int> &n_modes);
+    int finalize_coefs();
+    int finalize_shapes();
+    int finalize_ffat(const std::vector<int> &n_modes);
+    int upload_team_table(const TeamTable &t, DevBuf<TeamDesc> &d_teams, DevBuf<SplitObj> &d_split);
+    // step_chunk's stages, in the order they run (engine_launch.cpp); Launch: the record of one launch on step_chunk's stack
+    struct Launch;
+    int launch_wait_set(Launch &L);
+    int launch_plan(Launch &L);
+    int launch_open(Launch &L);
+    int launch_pack(Launch &L);
+    int launch_upload_and_gate(Launch &L);
+    int launch_expand_strokes(Launch &L);
+    int launch_bank_params(Launch &L);
+    int launch_prepare(Launch &L);
+    int launch_scan(Launch &L);
+    int launch_hand_over(Launch &L);
+    int launch_bank(Launch &L);
+    int launch_finish(Launch &L);
+    bool fuse_one_buffer_combine(int nb, int n_frows);
     int read_bus(const BusOut *o, int n_channels, const BusWords &w, float *out, size_t n);   // bus_state.h: the body of the four read_*()
     bool valid_obj(int obj) const { return obj >= 0 && obj < (int)objs_.size(); }
     int enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why, const pbso_track_play *play = nullptr,
@@ -415,8 +444,7 @@ private:
     // persistent device state
     DevBuf<float> d_ca_, d_cb_, d_sq_, d_sd_, d_ss_;
     DevBuf<double> d_c3_;
-    struct SizeClass { int W, first, count; };           // teams of W waves: d_teams_[first, first+count)
-    std::vector<SizeClass> classes_;
+    std::vector<SizeClass> classes_;                     // engine_tables.h: teams of W waves are d_teams_[first, first + count)
     DevBuf<TeamDesc> d_teams_;
     DevBuf<SplitObj> d_split_;                           // objects stepped by more than one team
     DevBuf<float> d_audio_parts_;                        // [n_part_rows_][nb * B] their partial sample sums
@@ -457,7 +485,9 @@ private:
     bool latency_path_ = true, last_one_stream_ = false;  // desc.latency_path; the previous launch prepared on the bank's stream
     int64_t tot_one_stream_launches_ = 0;
     int64_t tot_tc_launches_ = 0;
-    bool choose_time_chunks(int nb, int n_dense_rows, int *set, int *cb) const;
+    // launch_policy.h: the decisions of a launch are functions of these
+    PolicyScene policy_scene() const;
+    PolicySettings policy_settings() const;
     int n_cus_ = 256;                                     // hipDeviceProp_t::multiProcessorCount of the engine's device
     long long total_team_waves_ = 0;
     DevBuf<float> d_gq_;                                 // closed-form qnorm: G11, 2 G12, G22 planes
