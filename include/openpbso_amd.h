@@ -97,8 +97,13 @@ typedef struct pbso_engine pbso_engine;
 typedef struct pbso_engine_desc {
     int abi_version;          /* PBSO_ABI_VERSION */
     int device;               /* HIP device ordinal */
-    int frames_per_buffer;    /* 0 -> 513 (ModalSolver's BUF_SIZE template argument) */
-    int sample_rate;          /* 0 -> 44100 */
+    int frames_per_buffer;    /* 0 -> 513 (ModalSolver's BUF_SIZE template argument).  Any multiple of 27 up to 864; at a length
+                               * other than 513 both block forms silently run as PBSO_FORM_VELOCITY (pbso_engine_info says so),
+                               * time_chunks, PBSO_BANK_PIPE and the multi-listener mix do not apply, and from 702 frames on a
+                               * team of the per-sample kernel holds fewer than 16 waves (its LDS).  Tested against the oracle
+                               * at 27, 54, 270, 513, 540 and 864 frames. */
+    int sample_rate;          /* 0 -> 44100.  Any positive rate whose Nyquist frequency lies above the objects' modes; tested
+                               * against the oracle at 22050, 44100, 48000 and 96000 Hz. */
     int recurrence_form;      /* enum pbso_recurrence_form */
     int qnorm_mode;           /* enum pbso_qnorm_mode */
     int modes_per_lane;       /* 0 = auto; 1, 2, 3, 4 or 8 oscillators per lane (block form: 1, 2 or 4) */

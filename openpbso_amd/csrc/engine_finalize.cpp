@@ -190,7 +190,10 @@ int Engine::finalize_teams(const std::vector<int> &n_modes) {
     int rc;
     {
         // the engine's own shape
-        const int team_max = block ? MAX_WAVES_PER_BLOCK_TEAM : MAX_WAVES_PER_TEAM;
+        // (the per-sample kernel's LDS grows with the buffer length: no team larger than a CU's LDS holds at this n_tiles)
+        const int team_max = block ? MAX_WAVES_PER_BLOCK_TEAM : iir_team_cap_by_lds(n_tiles_, MAX_WAVES_PER_TEAM);
+        if (!block && iir_lds_bytes(team_max, n_tiles_) > IIR_LDS_LIMIT)
+            return fail(PBSO_ERR_INVALID, "frames_per_buffer: the per-sample kernel's tile ring does not fit the LDS");
         total_team_waves_ = total_waves(n_modes, R_);
         const int team_cap = engine_team_cap(total_team_waves_, n_cus_, team_max, desc_.team_waves);
         const TeamTable t = build_team_table(waves_per_object(n_modes, R_), R_, std::vector<int>(n_modes.size(), team_cap), MAX_WAVES_PER_TEAM);

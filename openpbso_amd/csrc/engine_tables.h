@@ -58,6 +58,15 @@ inline int engine_team_cap(long long waves, int n_cus, int team_max, int team_wa
     if (team_waves > 0) return std::min(team_max, team_waves);
     return (int)std::min<long long>(team_max, std::max<long long>(1, (waves + n_cus - 1) / n_cus));
 }
+// The per-sample bank's workgroup keeps a ring of n_tiles + 1 row-sum tiles per wave (kernels.h, iir_lds_bytes), so its LDS grows
+// with the buffer length: the largest team whose request a CU's 160 KB can hold -- 16 waves up to 25 tiles (675 frames), 15 from
+// 26, 14 at 32 (864 frames, where 16 waves would ask for 175 888 bytes).  Objects that need more waves are cut into several teams.
+constexpr size_t IIR_LDS_LIMIT = 160 * 1024;
+inline int iir_team_cap_by_lds(int n_tiles, int team_max) {
+    int w = std::max(1, team_max);
+    while (w > 1 && iir_lds_bytes(w, n_tiles) > IIR_LDS_LIMIT) --w;
+    return w;
+}
 
 // ---- team tables -----------------------------------------------------------------------------------------------------
 struct SizeClass { int W, first, count; };               // teams of W waves: teams[first, first + count)

@@ -1418,8 +1418,9 @@ __global__ __launch_bounds__(256) void mix_objects_stage1(const float *__restric
     if (i >= n) return;
     const int o0 = blockIdx.y * MIX_GROUP, o1 = o0 + MIX_GROUP < n_obj ? o0 + MIX_GROUP : n_obj;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    // rows are 8-byte aligned when the row length is even (n_buffers * 513 with an even n_buffers): two 8-byte loads per object,
-    // eight objects in flight; the adds stay in object order
+    // rows are 8-byte aligned when the row length n_buffers * frames_per_buffer is even (513 or 135 frames with an even n_buffers, any
+    // n_buffers of 270 or 864): two 8-byte loads per object, eight objects in flight; the adds stay in object order.  An odd row
+    // length (and the last, ragged quad of a row) takes the scalar path below
     const bool wide = (stride & 1) == 0 && i + 3 < n;
     if (wide) {
         int o = o0;

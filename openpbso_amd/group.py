@@ -20,13 +20,14 @@ def unique_id():
 
 class Group:
     def __init__(self, devices, world_size=0, first_rank=0, unique_id=None, form=None, qnorm=capi.QNORM_ALL, modes_per_lane=0,
-                 frames_per_buffer=0, transport=capi.GROUP_RCCL, **select):
+                 frames_per_buffer=0, transport=capi.GROUP_RCCL, sample_rate=0, **select):
         self._l = capi.lib()
         self.devices = list(devices)
         self.world = world_size or len(self.devices)
         self.first = first_rank
         self.qnorm_mode = qnorm
         self.B = frames_per_buffer or 513
+        self.sample_rate = sample_rate or 44100
         d = capi.GroupDesc()
         d.abi_version = capi.ABI_VERSION
         self._dev = (C.c_int * len(self.devices))(*self.devices)
@@ -37,7 +38,7 @@ class Group:
         d.transport = transport
         self._id = C.create_string_buffer(unique_id, capi.GROUP_ID_BYTES) if unique_id is not None else None
         d.unique_id = C.cast(self._id, C.c_void_p) if self._id is not None else None
-        fill_engine_desc(d.engine, 0, default_form() if form is None else form, qnorm, modes_per_lane, None, frames_per_buffer, select)
+        fill_engine_desc(d.engine, 0, default_form() if form is None else form, qnorm, modes_per_lane, None, frames_per_buffer, select, sample_rate)
         h = C.c_void_p()
         rc = self._l.pbso_group_create(C.byref(d), C.byref(h))
         self._h = h
@@ -117,7 +118,7 @@ class Group:
             if not h:
                 raise PbsoError(capi.ERR_INVALID, f"rank {rank} belongs to another process")
             lo, hi = self.span(rank)
-            self._engines[rank] = Engine.from_handle(h, [int(x) for x in self._modes[lo:hi]], self.qnorm_mode, self.B)
+            self._engines[rank] = Engine.from_handle(h, [int(x) for x in self._modes[lo:hi]], self.qnorm_mode, self.B, self.sample_rate)
         return self._engines[rank]
 
     def enqueue_force(self, global_id, msg, not_before=0):

@@ -137,11 +137,12 @@ SELECT_FIELDS = ("bank_kernel", "time_chunks", "direct_hits", "forced_block", "d
                  "time_chunk_shape", "scan_kernel", "fuse_short_launches", "submit_thread")
 
 
-def fill_engine_desc(d, device, form, qnorm, modes_per_lane, stream, frames_per_buffer, select):
+def fill_engine_desc(d, device, form, qnorm, modes_per_lane, stream, frames_per_buffer, select, sample_rate=0):
     """a capi.EngineDesc from the wrapper's arguments; returns the kernel / path selection that went into it"""
     d.abi_version = capi.ABI_VERSION
     d.device = device
     d.frames_per_buffer = frames_per_buffer
+    d.sample_rate = sample_rate
     d.recurrence_form = form
     d.qnorm_mode = qnorm
     d.modes_per_lane = modes_per_lane
@@ -162,7 +163,7 @@ def default_form():
 
 class Engine:
     @classmethod
-    def from_handle(cls, handle, n_modes, qnorm, frames_per_buffer=0):
+    def from_handle(cls, handle, n_modes, qnorm, frames_per_buffer=0, sample_rate=0):
         """a view of an engine somebody else owns (a device group's rank): same methods, close() leaves it alone"""
         self = cls.__new__(cls)
         self._l = capi.lib()
@@ -170,6 +171,7 @@ class Engine:
         self._owned = False
         self.n_modes = list(n_modes)
         self.B = frames_per_buffer or 513
+        self.sample_rate = sample_rate or 44100
         self.qnorm_mode = qnorm
         self._last_nb = 0
         self._borrowed = None
@@ -177,8 +179,9 @@ class Engine:
         return self
 
     def __init__(self, device=0, form=None, qnorm=capi.QNORM_ALL, modes_per_lane=0,
-                 stream=None, frames_per_buffer=0, **select):
-        """select: the ABI-4 fields of pbso_engine_desc that pick kernels and paths for THIS engine (bank_kernel,
+                 stream=None, frames_per_buffer=0, sample_rate=0, **select):
+        """frames_per_buffer (a multiple of 27, at most 864) / sample_rate: 0 = the reference's 513 / 44100.
+        select: the ABI-4 fields of pbso_engine_desc that pick kernels and paths for THIS engine (bank_kernel,
         time_chunks, direct_hits, ...; include/openpbso_amd.h).  0 / absent = the engine's policy."""
         if form is None:
             # the C ABI's default (a zeroed pbso_engine_desc): the block form with the exact f32 projection.
@@ -187,7 +190,7 @@ class Engine:
         self.form = form
         self._l = capi.lib()
         d = capi.EngineDesc()
-        self.select = fill_engine_desc(d, device, form, qnorm, modes_per_lane, stream, frames_per_buffer, select)
+        self.select = fill_engine_desc(d, device, form, qnorm, modes_per_lane, stream, frames_per_buffer, select, sample_rate)
         self._owned = True
         h = C.c_void_p()
         rc = self._l.pbso_engine_create(C.byref(d), C.byref(h))
@@ -200,6 +203,7 @@ class Engine:
             raise PbsoError(rc, text)
         self.n_modes = []
         self.B = frames_per_buffer or 513
+        self.sample_rate = sample_rate or 44100
         self.qnorm_mode = qnorm
         self._last_nb = 0
         self._borrowed = None

@@ -47,23 +47,44 @@ def build(native=False):
     return os.path.join(_HERE, "libpbso_oracle_native.so" if native else "libpbso_oracle.so")
 
 
+def build_variant(frames, rate):
+    """(Re)build the variant library compiled for `frames` samples per buffer at `rate` Hz. Returns the .so path."""
+    name = f"libpbso_oracle_f{int(frames)}_r{int(rate)}.so"
+    subprocess.run(["make", "-C", _HERE, name, f"FRAMES={int(frames)}", f"RATE={int(rate)}"], check=True, capture_output=True)
+    return os.path.join(_HERE, name)
+
+
 _lib = None
+_variants = {}
 
 
-def lib(native=False):
+def _load(path, rebuild):
+    src_m = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("pbso_oracle.c", "pbso_oracle.h"))
+    if not os.path.exists(path) or os.path.getmtime(path) < src_m:
+        rebuild()
+    try:
+        return _bind(C.CDLL(path))
+    except OSError:
+        rebuild()
+        return _bind(C.CDLL(path))
+
+
+def lib(native=False, frames=None, rate=None):
+    """The default library (the reference's 513 frames at 44100 Hz), or with frames= / rate= the variant compiled for that
+    pair, built on demand.  Every library carries its own .B, .rate and .h = 1 / rate."""
     global _lib
     if native:
         return _bind(C.CDLL(build(native=True)))
+    if frames is not None or rate is not None:
+        key = (int(B if frames is None else frames), int(SAMPLE_RATE if rate is None else rate))
+        if key not in _variants:
+            path = os.path.join(_HERE, f"libpbso_oracle_f{key[0]}_r{key[1]}.so")
+            l = _load(path, lambda: build_variant(*key))
+            assert (l.B, l.rate) == key, (l.B, l.rate, key)
+            _variants[key] = l
+        return _variants[key]
     if _lib is None:
-        path = os.path.join(_HERE, "libpbso_oracle.so")
-        src_m = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("pbso_oracle.c", "pbso_oracle.h"))
-        if not os.path.exists(path) or os.path.getmtime(path) < src_m:
-            build()
-        try:
-            _lib = _bind(C.CDLL(path))
-        except OSError:
-            build()
-            _lib = _bind(C.CDLL(path))
+        _lib = _load(os.path.join(_HERE, "libpbso_oracle.so"), build)
     return _lib
 
 
@@ -141,6 +162,14 @@ def _bind(l):
     l.or_bench_run.restype = C.c_double
     l.or_bench_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_double, C.c_double,
                                C.c_double, dp, C.c_char_p, dp, C.c_int]
+    # the two constants this library was compiled with
+    l.or_frames_per_buffer.restype = C.c_int
+    l.or_frames_per_buffer.argtypes = []
+    l.or_sample_rate.restype = C.c_int
+    l.or_sample_rate.argtypes = []
+    l.B = l.or_frames_per_buffer()
+    l.rate = l.or_sample_rate()
+    l.h = 1.0 / l.rate
     return l
 
 
@@ -158,22 +187,26 @@ def iir_coeffs(omega2, density, alpha, beta, h=1.0 / SAMPLE_RATE):
     return c1, c2, c3
 
 
-def make_force(kind, width_us=0.0):
+def make_force(kind, width_us=0.0, l=None):
+    """l: the library (lib(frames=, rate=)) whose rate sizes a Gaussian and whose buffer length force_add fills"""
+    l = lib() if l is None else l
     f = OrForce()
+    f._l = l
     if kind == POINT:
-        lib().or_force_init_point(C.byref(f))
+        l.or_force_init_point(C.byref(f))
     elif kind == GAUSSIAN:
-        lib().or_force_init_gaussian(C.byref(f), float(width_us))
+        l.or_force_init_gaussian(C.byref(f), float(width_us))
     elif kind == AR:
-        lib().or_force_init_ar(C.byref(f))
+        l.or_force_init_ar(C.byref(f))
     else:
         raise ValueError(kind)
     return f
 
 
 def force_add(f, buf):
-    assert buf.dtype == np.float64 and buf.size == B
-    return bool(lib().or_force_add(C.byref(f), _dp(buf)))
+    l = getattr(f, "_l", None) or lib()
+    assert buf.dtype == np.float64 and buf.size == l.B
+    return bool(l.or_force_add(C.byref(f), _dp(buf)))
 
 
 def modal_force_vertex(modes, vid, vn, n=None):
@@ -224,18 +257,21 @@ def map_psi(m):
 class Solver:
     """Mirror of ModalSolver<double> (modal_solver.h:100-179) over the C oracle."""
 
-    def __init__(self, omega2, density, alpha, beta, n_modes=None, h=1.0 / SAMPLE_RATE):
+    def __init__(self, omega2, density, alpha, beta, n_modes=None, h=None, l=None):
+        """l: the library to step with (lib(frames=, rate=)); its buffer length and, unless h is given, its 1 / rate apply"""
+        self._l = lib() if l is None else l
+        self.B = self._l.B
         om = np.ascontiguousarray(omega2, dtype=np.float64)
         self.n = om.size if n_modes is None else n_modes
-        self._s = lib().or_solver_new(self.n)
-        it = lib().or_integrator_build(density, _dp(om), om.size, alpha, beta, h, self.n)
+        self._s = self._l.or_solver_new(self.n)
+        it = self._l.or_integrator_build(density, _dp(om), om.size, alpha, beta, self._l.h if h is None else h, self.n)
         assert it, "N for modal integrator invalid"
-        lib().or_solver_set_integrator(self._s, it)
+        self._l.or_solver_set_integrator(self._s, it)
         self._maps = None
 
     def close(self):
         if self._s:
-            lib().or_solver_free(self._s)
+            self._l.or_solver_free(self._s)
             self._s = None
 
     def __del__(self):
@@ -246,39 +282,39 @@ class Solver:
 
     def read_ffat_maps(self, maps):
         arr = (OrFfatMap * len(maps))(*maps)
-        lib().or_solver_set_ffat_maps(self._s, arr, len(maps))
+        self._l.or_solver_set_ffat_maps(self._s, arr, len(maps))
 
     def enqueue_force(self, data, force=None, sustained_start=False, sustained_end=False, clear_all=False):
         d = np.ascontiguousarray(data, dtype=np.float64)
         fp = C.byref(force) if force is not None else None
-        return bool(lib().or_solver_enqueue_force(self._s, _dp(d), d.size, fp, int(sustained_start),
+        return bool(self._l.or_solver_enqueue_force(self._s, _dp(d), d.size, fp, int(sustained_start),
                                                   int(sustained_end), int(clear_all)))
 
     def enqueue_arprm(self, a, sigma, mu):
         a = np.ascontiguousarray(a, dtype=np.float64)
-        return bool(lib().or_solver_enqueue_arprm(self._s, _dp(a), sigma, mu))
+        return bool(self._l.or_solver_enqueue_arprm(self._s, _dp(a), sigma, mu))
 
     def compute_transfer(self, pos):
         p = np.ascontiguousarray(pos, dtype=np.float64)
-        return lib().or_solver_compute_transfer(self._s, _dp(p))
+        return self._l.or_solver_compute_transfer(self._s, _dp(p))
 
     def compute_transfer_out(self, pos, n):
         p = np.ascontiguousarray(pos, dtype=np.float64)
         out = np.empty(n)
-        rc = lib().or_solver_compute_transfer_out(self._s, _dp(p), _dp(out))
+        rc = self._l.or_solver_compute_transfer_out(self._s, _dp(p), _dp(out))
         return rc, out
 
     def set_use_transfer(self, use):
-        lib().or_solver_set_use_transfer(self._s, int(use))
+        self._l.or_solver_set_use_transfer(self._s, int(use))
 
     def latest_transfer(self):
-        return np.ctypeslib.as_array(lib().or_solver_latest_transfer(self._s), shape=(self.n,)).copy()
+        return np.ctypeslib.as_array(self._l.or_solver_latest_transfer(self._s), shape=(self.n,)).copy()
 
     def step(self):
-        """returns (sound[513], qnorm[n]) or None when the step returned early."""
-        sound = np.empty(B)
+        """returns (sound[B], qnorm[n]) or None when the step returned early."""
+        sound = np.empty(self.B)
         qn = np.empty(max(self.n, 1))
-        rc = lib().or_solver_step(self._s, _dp(sound), _dp(qn))
+        rc = self._l.or_solver_step(self._s, _dp(sound), _dp(qn))
         if rc < 0:
             raise AssertionError("reference assert would fire (sustained force list size != 1)")
         if rc == 0:
@@ -286,9 +322,9 @@ class Solver:
         return sound, qn[: self.n]
 
     def n_active(self):
-        return lib().or_solver_n_active(self._s)
+        return self._l.or_solver_n_active(self._s)
 
     def state(self):
-        q1 = np.ctypeslib.as_array(lib().or_solver_state(self._s, 0), shape=(self.n,)).copy()
-        q2 = np.ctypeslib.as_array(lib().or_solver_state(self._s, 1), shape=(self.n,)).copy()
+        q1 = np.ctypeslib.as_array(self._l.or_solver_state(self._s, 0), shape=(self.n,)).copy()
+        q2 = np.ctypeslib.as_array(self._l.or_solver_state(self._s, 1), shape=(self.n,)).copy()
         return q1, q2

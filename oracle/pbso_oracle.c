@@ -22,6 +22,9 @@
 
 #define B OR_FRAMES_PER_BUFFER
 
+int or_frames_per_buffer(void) { return OR_FRAMES_PER_BUFFER; }
+int or_sample_rate(void) { return OR_SAMPLE_RATE; }
+
 /* ========================================================================== */
 /* A1  modal_integrator.h:47-70  (Build: Rayleigh damping -> a, b)             */
 /* ========================================================================== */

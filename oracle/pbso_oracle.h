@@ -34,8 +34,16 @@
 extern "C" {
 #endif
 
+/* the reference's two constants; -D builds a variant library for another buffer length / rate (oracle/Makefile) */
+#ifndef OR_SAMPLE_RATE
 #define OR_SAMPLE_RATE 44100        /* config.h:13 */
+#endif
+#ifndef OR_FRAMES_PER_BUFFER
 #define OR_FRAMES_PER_BUFFER 513    /* config.h:14 */
+#endif
+/* what this library was compiled with */
+int or_frames_per_buffer(void);
+int or_sample_rate(void);
 
 /* ---- A1: ModalIntegrator<double>::Build + ctor (modal_integrator.h:47-101) */
 void or_build_ab(double density, const double *omega_squared, int n,

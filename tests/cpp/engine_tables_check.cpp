@@ -177,6 +177,23 @@ static void team_tables() {
                   !std::memcmp(p.split.data(), h.split.data(), h.split.size() * sizeof(SplitObj)));
         CHECK(pipe_chunks(n_modes) == (long long)h.teams.size());
     }
+    // the per-sample bank's team size by LDS: whatever the buffer length, the chosen team's request fits a CU's 160 KB and one more
+    // wave would not (or is not allowed); 513 frames keep their 16 waves, 864 frames cannot
+    for (int nt = 1; nt <= MAX_TILES; ++nt) {
+        const int cap = iir_team_cap_by_lds(nt, MAX_WAVES_PER_TEAM);
+        CHECK(cap >= 1 && cap <= MAX_WAVES_PER_TEAM);
+        CHECK(iir_lds_bytes(cap, nt) <= 160 * 1024);
+        CHECK(cap == MAX_WAVES_PER_TEAM || iir_lds_bytes(cap + 1, nt) > 160 * 1024);
+        for (int tw : {0, 1, 3, 16, 99}) {                                   // whatever the caller asks for, and on a full chip
+            const int c = engine_team_cap(1 << 20, 256, cap, tw);
+            CHECK(c >= 1 && c <= cap && iir_lds_bytes(c, nt) <= 160 * 1024);
+        }
+        CHECK(iir_team_cap_by_lds(nt, 4) == 4);
+    }
+    CHECK(MAX_TILES == 32);
+    CHECK(iir_team_cap_by_lds(19, MAX_WAVES_PER_TEAM) == 16);
+    CHECK(iir_team_cap_by_lds(25, MAX_WAVES_PER_TEAM) == 16 && iir_team_cap_by_lds(26, MAX_WAVES_PER_TEAM) == 15);
+    CHECK(iir_team_cap_by_lds(32, MAX_WAVES_PER_TEAM) == 14 && iir_lds_bytes(16, 32) == 175888);
     // the policy's modes per lane at 256 CUs: the fewest whose waves fit (8 per CU in the block form, 16 per sample)
     CHECK(choose_modes_per_lane(std::vector<int>(256, 512), true, 256) == 1);      // 2048 waves
     CHECK(choose_modes_per_lane(std::vector<int>(512, 512), true, 256) == 2);

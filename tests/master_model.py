@@ -9,7 +9,7 @@ import tempfile
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-B = 513
+B = 513                                  # the default buffer length (Model(frames=...) takes any other)
 METER_DTYPE = np.dtype([("in_peak", np.float32), ("out_peak", np.float32), ("min_gain", np.float32), ("n_limited", np.int32),
                         ("sumsq", np.float64)])
 _lib = None
@@ -53,7 +53,8 @@ def evaluate(v, L, H, T, w):
 
 
 class Model:
-    def __init__(self, n_channels, ceiling, lookahead, hold, ramp, w=None):
+    def __init__(self, n_channels, ceiling, lookahead, hold, ramp, w=None, frames=B):
+        self.B = frames                                                    # the meters' buffer length
         self.C, self.T, self.L, self.H, self.R = n_channels, float(np.float32(ceiling)), lookahead, hold, ramp
         self.HL = 2 * lookahead + hold
         self.w = window(lookahead) if w is None else np.asarray(w, dtype=np.float32)
@@ -84,7 +85,7 @@ class Model:
         self.t, self.frm, self.slope, self.t_set = 0, self.to, 0.0, 0
 
     def process(self, input):
-        """input [C][n] float32, the next step (n a multiple of 513 for the meters) -> y [C][n]; self.meters [n // 513][C]"""
+        """input [C][n] float32, the next step (n a multiple of the buffer length for the meters) -> y [C][n]; self.meters [n // B][C]"""
         u = np.asarray(input, dtype=np.float32).reshape(self.C, -1)
         n = u.shape[1]
         p = self._p(self.t + np.arange(n)).astype(np.float32)
@@ -95,6 +96,7 @@ class Model:
         self.tail = np.ascontiguousarray(vv[:, vv.shape[1] - self.HL:])
         self.t += n
         self.gains = g
+        B = self.B
         if n % B == 0:
             nb = n // B
             m = np.zeros((nb, self.C), dtype=METER_DTYPE)

@@ -31,8 +31,17 @@ class ObjSpec:
         self.rho, self.alpha, self.beta = rho, alpha, beta
 
 
-def run_engine(objs, events, n_buffers, split=None, **engine_kw):
-    """returns dict(audio [n_obj][NB*513] f32, emitted, qnorm {(obj,buf): arr}, state, info)"""
+def _oracle_lib(frames, rate):
+    """the default library for the reference's 513 / 44100, the variant compiled for any other pair"""
+    return orc.lib() if (frames, rate) == (B, orc.SAMPLE_RATE) else orc.lib(frames=frames, rate=rate)
+
+
+def run_engine(objs, events, n_buffers, split=None, frames=B, rate=orc.SAMPLE_RATE, **engine_kw):
+    """returns dict(audio [n_obj][NB*frames] f32, emitted, qnorm {(obj,buf): arr}, state, info)"""
+    if frames != B:
+        engine_kw.setdefault("frames_per_buffer", frames)
+    if rate != orc.SAMPLE_RATE:
+        engine_kw.setdefault("sample_rate", rate)
     eng = Engine(**engine_kw)
     try:
         for o in objs:
@@ -85,12 +94,14 @@ def _oracle_maps(maps):
     return out
 
 
-def _oracle_one(oi, o, events, n_buffers):
-    """one object through the oracle; returns (audio row, emitted row, {buffer: qnorm}, state, latest)"""
+def _oracle_one(oi, o, events, n_buffers, l=None):
+    """one object through the oracle library l; returns (audio row, emitted row, {buffer: qnorm}, state, latest)"""
+    l = orc.lib() if l is None else l
+    B = l.B
     audio = np.zeros(n_buffers * B)
     emitted = np.ones(n_buffers, dtype=bool)
     qn = {}
-    s = orc.Solver(o.lam, o.rho, o.alpha, o.beta, n_modes=o.n_modes)
+    s = orc.Solver(o.lam, o.rho, o.alpha, o.beta, n_modes=o.n_modes, l=l)
     if o.maps is not None:
         s.read_ffat_maps(_oracle_maps(o.maps))
     evs = sorted([e for e in events if e["obj"] == oi], key=lambda e: e["t"])
@@ -115,7 +126,7 @@ def _oracle_one(oi, o, events, n_buffers):
                     data = orc.modal_force_face(o.shapes, ev["vids"], ev["coords"], ev["vn"], n)
                 else:
                     data = np.zeros(n)
-                f = orc.make_force(ev["force_type"], ev["width"])
+                f = orc.make_force(ev["force_type"], ev["width"], l)
                 assert s.enqueue_force(data, f, ev["start"], ev["end"], ev["clear"])
             else:
                 gui.append(ev)
@@ -141,18 +152,19 @@ def _oracle_one(oi, o, events, n_buffers):
     return out
 
 
-def run_oracle(objs, events, n_buffers, only=None, threads=1):
+def run_oracle(objs, events, n_buffers, only=None, threads=1, frames=B, rate=orc.SAMPLE_RATE):
     """same outputs in float64 from oracle/ (the reference's semantics).  `only`: object ids to run
     (rows of the result keep the order of `only`); threads > 1 runs objects side by side (they are
     independent, and the oracle calls release the GIL)."""
     ids = list(range(len(objs))) if only is None else list(only)
+    l = _oracle_lib(frames, rate)
     if threads > 1 and len(ids) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=threads) as ex:
-            res = list(ex.map(lambda oi: _oracle_one(oi, objs[oi], events, n_buffers), ids))
+            res = list(ex.map(lambda oi: _oracle_one(oi, objs[oi], events, n_buffers, l), ids))
     else:
-        res = [_oracle_one(oi, objs[oi], events, n_buffers) for oi in ids]
-    audio = np.array([r[0] for r in res]).reshape(len(ids), n_buffers * B)
+        res = [_oracle_one(oi, objs[oi], events, n_buffers, l) for oi in ids]
+    audio = np.array([r[0] for r in res]).reshape(len(ids), n_buffers * frames)
     emitted = np.array([r[1] for r in res]).reshape(len(ids), n_buffers)
     qn = {(k, b): v for k, r in enumerate(res) for b, v in r[2].items()}
     return dict(audio=audio, emitted=emitted, qnorm=qn, state=[r[3] for r in res], latest=[r[4] for r in res])

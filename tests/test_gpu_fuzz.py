@@ -57,25 +57,26 @@ def random_script(rng, n_obj, n_modes, nb, with_maps):
     return evs
 
 
-def _legal(evs, objs, nb):
+def _legal(evs, objs, nb, frames=513, rate=44100):
     """drop scripts the reference itself would abort on (clearAllForces while sustained leaves
     _sustainedForces set with an empty list: assert at modal_solver.h:223)"""
     try:
-        run_oracle(objs, evs, nb)
+        run_oracle(objs, evs, nb, frames=frames, rate=rate)
         return True
     except AssertionError:
         return False
 
 
-def _run_seed(seed, size_choices, engine_kw, projected_hits=False):
+def seed_scene(seed, size_choices, projected_hits=False, f_hi=None, nb_range=(6, 16)):
+    """the scene, script and steps of a seed: (objs, evs, nb, split)"""
     rng = np.random.default_rng(1000 + seed)
     n_obj = int(rng.integers(1, 5))
     n_modes = [int(rng.choice(size_choices)) for _ in range(n_obj)]
-    nb = int(rng.integers(6, 16))
+    nb = int(rng.integers(*nb_range))
     with_maps = [bool(rng.random() < 0.5) for _ in range(n_obj)]
     objs = []
     for oi in range(n_obj):
-        lam = synth.eigenvalues(n_modes[oi], 5000 + 10 * seed + oi)
+        lam = synth.eigenvalues(n_modes[oi], 5000 + 10 * seed + oi, **({} if f_hi is None else dict(f_hi=f_hi)))
         objs.append(ObjSpec(lam, shapes=synth.mode_shapes(n_modes[oi], 6000 + seed + oi) if projected_hits else None,
                             maps=synth.ffat_maps(lam, 7000 + seed + oi, dim=4) if with_maps[oi] else None))
     evs = random_script(rng, n_obj, n_modes, nb, with_maps)
@@ -91,14 +92,21 @@ def _run_seed(seed, size_choices, engine_kw, projected_hits=False):
                 else:
                     bary = rng.random(3)
                     e["vids"], e["coords"] = rng.integers(0, synth.N_VERTS, 3), bary / bary.sum()
-    if not _legal(evs, objs, nb):
-        pytest.skip("script trips a live assert of the reference")
     split = None
     if nb > 8:
         k = int(rng.integers(1, nb - 1))
         split = [k, nb - k]
-    got = run_engine(objs, evs, nb, split=split, **engine_kw)
-    want = run_oracle(objs, evs, nb)
+    return objs, evs, nb, split
+
+
+def _run_seed(seed, size_choices, engine_kw, projected_hits=False, frames=513, rate=44100, f_hi=None, nb_range=(6, 16)):
+    objs, evs, nb, split = seed_scene(seed, size_choices, projected_hits, f_hi, nb_range)
+    if not _legal(evs, objs, nb, frames, rate):
+        pytest.skip("script trips a live assert of the reference")
+    got = run_engine(objs, evs, nb, split=split, frames=frames, rate=rate, **engine_kw)
+    want = run_oracle(objs, evs, nb, frames=frames, rate=rate)
+    print(f"seed {seed} frames {frames} rate {rate}: max/peak {rel_errors(got['audio'], want['audio'])[0].max():.3e} "
+          f"l2 {rel_errors(got['audio'], want['audio'])[1].max():.3e}")
     assert np.array_equal(got["emitted"], want["emitted"])
     mx, l2 = rel_errors(got["audio"], want["audio"])
     assert (mx <= 5e-4).all() and (l2 <= 1e-3).all(), (mx, l2)

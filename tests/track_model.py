@@ -18,7 +18,9 @@ import numpy as np
 from openpbso_amd import Engine, ForceMessage, capi
 from openpbso_amd.solver import PbsoError
 from oracle import oracle_py as orc
-from tests.scenarios import B, force_ev
+from tests.scenarios import force_ev
+
+FRAMES, RATE = 513, 44100                  # the defaults of every frames= / rate= below: the reference's buffer
 
 class EngineRefused(Exception):
     """pbso_engine_create or pbso_finalize refused the descriptor (a combination of options the engine does not run)"""
@@ -30,7 +32,7 @@ UNIT_TRANSFER = 1e7
 
 # ---------------------------------------------------------------------------
 # profiles: closures that return the buffer's profile, or None when Force::Add returns false
-def point_profile():
+def point_profile(B=FRAMES):
     state = {"used": False}
 
     def f():
@@ -43,8 +45,8 @@ def point_profile():
     return f
 
 
-def gauss_profile(width_us):
-    w = max(1, int(width_us / 1000000. * 44100))
+def gauss_profile(width_us, B=FRAMES, rate=RATE):
+    w = max(1, int(width_us / 1000000. * rate))
     st = {"count": 0, "center": int(4.5 * w)}
 
     def f():
@@ -88,7 +90,7 @@ def track_value(s, first, rate, gain, loop, k):
     return gain * (s0 + f * (s1 - s0))
 
 
-def track_profile(samples, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sample=0, loop=False):
+def track_profile(samples, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sample=0, loop=False, B=FRAMES):
     s = np.asarray(samples, dtype=np.float32)              # a track is f32 in device memory
     N = track_total(len(s), first, rate, n_samples, loop)
     st = {"k0": 0, "o": start_sample}
@@ -114,8 +116,8 @@ def track_profile(samples, first=0.0, rate=1.0, gain=1.0, n_samples=0, start_sam
 class TrackSolver:
     """one ModalSolver<double> (modal_solver.h:181-276), the bookkeeping of PySolver"""
 
-    def __init__(self, c1, c2, c3):
-        self.c1, self.c2, self.c3 = c1, c2, c3
+    def __init__(self, c1, c2, c3, frames=FRAMES):
+        self.c1, self.c2, self.c3, self.B = c1, c2, c3, frames
         self.q1 = np.zeros_like(c1)
         self.q2 = np.zeros_like(c1)
         self.queue, self.active, self.sustained = [], [], False
@@ -144,7 +146,7 @@ class TrackSolver:
                 self.active[0]["data"] = m["data"]
             if m.get("end"):
                 self.active, self.sustained = [], False
-        T = np.zeros(B)
+        T = np.zeros(self.B)
         S = np.zeros_like(self.c1)
         keep = []
         track_added = False
@@ -166,9 +168,9 @@ class TrackSolver:
 
     def samples(self, S, T):
         """modal_solver.h:258-273: the buffer's samples and its qnorm row, with the transfer in force"""
-        out = np.zeros(B)
+        out = np.zeros(self.B)
         qn = np.zeros_like(self.c1)
-        for i in range(B):
+        for i in range(self.B):
             q = (self.c1 * self.q1 + self.c2 * self.q2) + self.c3 * (S * T[i])
             self.q2, self.q1 = self.q1, q
             out[i] = float(np.dot(q, self.transfer))
@@ -180,7 +182,7 @@ class TrackSolver:
         return None if st is None else self.samples(*st)
 
 
-def lfilter_run(c1, c2, c3, forcing):
+def lfilter_run(c1, c2, c3, forcing, B=FRAMES):
     """the emitted buffers `forcing` = [(S, T, transfer)] of a run at once, from rest; returns (audio, qnorm rows, (q1, q2))"""
     from scipy.signal import lfilter
     n, nb = len(c1), len(forcing)
@@ -214,22 +216,23 @@ def _data_of(o, ev):
     return np.zeros(n)
 
 
-def _profile_of(ev, tracks):
+def _profile_of(ev, tracks, B=FRAMES, rate=RATE):
     if ev.get("track") is not None:
         p = dict(ev["track"])
-        return track_profile(tracks[p.pop("track")], **p)
+        return track_profile(tracks[p.pop("track")], B=B, **p)
     if ev["force_type"] == capi.POINT_FORCE:
-        return point_profile()
+        return point_profile(B)
     if ev["force_type"] == capi.GAUSSIAN_FORCE:
-        return gauss_profile(ev["width"])
+        return gauss_profile(ev["width"], B, rate)
     raise ValueError("the model plays point, Gaussian and track forces")
 
 
-def model_one(oi, o, tracks, events, n_buffers, per_sample=True):
+def model_one(oi, o, tracks, events, n_buffers, per_sample=True, frames=FRAMES, rate=RATE):
     """one object through the model: (audio, emitted, {buffer: qnorm}, (q1, q2), track rows, accepted flags of its force events)"""
-    c1, c2, c3 = orc.iir_coeffs(o.lam, o.rho, o.alpha, o.beta)
+    B = frames
+    c1, c2, c3 = orc.iir_coeffs(o.lam, o.rho, o.alpha, o.beta, h=1.0 / rate)
     c1, c2, c3 = c1[:o.n_modes], c2[:o.n_modes], c3[:o.n_modes]
-    s = TrackSolver(c1, c2, c3)
+    s = TrackSolver(c1, c2, c3, B)
     helper = None
     if o.maps is not None:                                   # the transfer vector a listener position selects: the oracle's own lookup
         from tests.scenarios import _oracle_maps
@@ -246,7 +249,7 @@ def model_one(oi, o, tracks, events, n_buffers, per_sample=True):
             ev = evs[ei]
             ei += 1
             if ev["kind"] == "force":
-                accepted.append(s.enqueue(dict(data=_data_of(o, ev), profile=None if ev["clear"] else _profile_of(ev, tracks),
+                accepted.append(s.enqueue(dict(data=_data_of(o, ev), profile=None if ev["clear"] else _profile_of(ev, tracks, B, rate),
                                                start=ev["start"], end=ev["end"], clear=ev["clear"])))
             elif ev["kind"] == "listener":
                 if queued_transfer is None:                 # the 1-slot queue: a second position before the step is dropped
@@ -273,7 +276,7 @@ def model_one(oi, o, tracks, events, n_buffers, per_sample=True):
             s.forcing.append((st[0], st[1], s.transfer.copy()))
     if not per_sample and s.forcing:
         keep = np.flatnonzero(emitted)
-        a, rows, (s.q1, s.q2) = lfilter_run(c1, c2, c3, s.forcing)
+        a, rows, (s.q1, s.q2) = lfilter_run(c1, c2, c3, s.forcing, B)
         for j, b in enumerate(keep):
             audio[b * B:(b + 1) * B] = a[j * B:(j + 1) * B]
             qn[int(b)] = rows[j]
@@ -282,11 +285,11 @@ def model_one(oi, o, tracks, events, n_buffers, per_sample=True):
     return audio, emitted, qn, (s.q1, s.q2), s.track_rows, accepted
 
 
-def run_model(objs, tracks, events, n_buffers, only=None, per_sample=True):
+def run_model(objs, tracks, events, n_buffers, only=None, per_sample=True, frames=FRAMES, rate=RATE):
     """scenarios.run_oracle's outputs from the model, plus track_rows (summed over the objects run) and the accepted flags"""
     ids = list(range(len(objs))) if only is None else list(only)
-    res = [model_one(oi, objs[oi], tracks, events, n_buffers, per_sample) for oi in ids]
-    return dict(audio=np.array([r[0] for r in res]).reshape(len(ids), n_buffers * B),
+    res = [model_one(oi, objs[oi], tracks, events, n_buffers, per_sample, frames, rate) for oi in ids]
+    return dict(audio=np.array([r[0] for r in res]).reshape(len(ids), n_buffers * frames),
                 emitted=np.array([r[1] for r in res]).reshape(len(ids), n_buffers),
                 qnorm={(k, b): v for k, r in enumerate(res) for b, v in r[2].items()}, state=[r[3] for r in res],
                 track_rows=sum(r[4] for r in res), accepted=[r[5] for r in res])
@@ -316,9 +319,13 @@ def feed_event(eng, ev, track_ids):
     return True
 
 
-def run_engine(objs, tracks, events, split, per_step=False, extra=None, **engine_kw):
+def run_engine(objs, tracks, events, split, per_step=False, extra=None, frames=FRAMES, rate=RATE, **engine_kw):
     """scenarios.run_engine with tracks: the steps of `split`, the whole script fed before the first step or (per_step) every
     step its own events just before it; returns audio, emitted, qnorm, state, track_stats, stroke_stats, accepted, info"""
+    if frames != FRAMES:
+        engine_kw.setdefault("frames_per_buffer", frames)
+    if rate != RATE:
+        engine_kw.setdefault("sample_rate", rate)
     try:
         eng = Engine(**engine_kw)
     except PbsoError as e:
