@@ -449,6 +449,38 @@ int pbso_read_state(pbso_engine *e, int object_id, double *q1, double *q2, int n
  * fp32; modes beyond n keep their state).  Force lists, queues and the transfer in effect are not part of it:
  * a resumed run re-sends its pending messages.  Waits for the launches in flight.                              */
 int pbso_write_state(pbso_engine *e, int object_id, const double *q1, const double *q2, int n);
+
+/* --- retune: a new material for objects of a finalized engine ------------------------------------------------------------------
+ * ModalSolver::setIntegrator (modal_solver.h:142-144) swaps the integrator of a live solver; the tool rebuilds its solver when a
+ * new model is loaded (tools/real_time_modal_sound.cpp:446-455).  pbso_set_material gives objects object_ids[0 .. n-1] the
+ * materials materials[0 .. n-1]: the host evaluates c1, c2, c3 of every mode (modal_integrator.h:63-99, the code pbso_add_object
+ * runs), uploads 24 bytes per mode, and kernels rebuild every coefficient table of the named objects on the device, bit for bit
+ * as pbso_finalize would have built them for that material (kernels_retune.hip; the tables are fp64 chains of + and x).
+ * WHEN.  After pbso_finalize, between steps.  It takes effect at the first sample of the next step, for every sample of that
+ *   step on.  Nothing of an earlier step changes.
+ * WHAT DOES NOT CHANGE.  The mode count of an object stays as given to pbso_add_object (the reference's numModesAudible is not
+ *   re-applied for the new density).  FFAT maps and their k, listener paths, transfer rows, tracks and queued messages are
+ *   untouched: the maps were computed for the material they were loaded with, and stay that material's.
+ * FORCES.  A force's modal vector g = (float)(c3 . S) is formed per launch from the force's data and the c3 table, and the
+ *   vertex-hit rows (float)(c3 . shape) are rebuilt with the tables: a force alive across the call goes on with the new c3, and
+ *   so does a message enqueued before the call for a stamp after it.  Nothing computed from c3 is kept from enqueue time.
+ * KEEP_STATE.  keep_state != 0: the state pbso_read_state returns is the same immediately before and after the call; the
+ *   displacement carries on under the new coefficients (a material slider).  keep_state == 0: q_{k-1} = q_{k-2} = 0 for the
+ *   named objects -- the reference's setIntegrator with a freshly built integrator, whose state lives in the integrator.
+ * ALL OR NOTHING.  Everything is validated before the device is touched; on any error nothing has changed.  PBSO_ERR_STATE
+ *   before pbso_finalize (or after a step that failed half-way).  PBSO_ERR_INVALID: n < 0, a NULL array with n > 0, an id out of
+ *   range, an id named twice, a value that is not finite, density <= 0, or any mode whose new c1, c2 or c3 is not finite (an
+ *   over-damped mode) -- stricter than pbso_add_object, on purpose, for a live engine.  n == 0 is accepted.
+ * COST.  A control operation, not a hot-loop call: it first drains the engine -- the submitting thread's queue, every stream,
+ *   the launch in flight --, runs the rebuild on the engine's stream and returns when the tables are in place: it costs a
+ *   device synchronisation.  After pbso_listeners_enable, pbso_mix_listeners of a retuned object needs a step after the call. */
+typedef struct pbso_material { double density, alpha, beta; } pbso_material;      /* 24 bytes */
+int pbso_set_material(pbso_engine *e, int n, const int *object_ids, const pbso_material *materials, int keep_state);
+/* the material in force: the one given to pbso_add_object, or the last accepted pbso_set_material */
+int pbso_get_material(pbso_engine *e, int object_id, pbso_material *out);
+/* totals since the engine was created: out[0] pbso_set_material calls accepted, out[1] objects retuned, out[2] modes rebuilt
+ * (padding columns not counted), out[3] g32 elements rebuilt (dof x padded modes of the retuned objects that have shapes) */
+int pbso_material_stats(pbso_engine *e, int64_t out[4]);
 void *pbso_audio_device_ptr(pbso_engine *e);
 
 /* Sum over the engine's objects of the LAST step's audio, on the device, in object order (deterministic):
@@ -702,6 +734,10 @@ int pbso_group_finalize(pbso_group *g);
 pbso_engine *pbso_group_engine(pbso_group *g, int rank);                      /* NULL for a rank of another process */
 /* pbso_enqueue_force on the object's owner (1 / 0 / < 0); an object of another process: 1, nothing done (its owner does it) */
 int pbso_group_enqueue_force(pbso_group *g, int global_id, const pbso_force_msg *m, int64_t not_before);
+/* pbso_set_material on the owners of global_ids[0 .. n-1].  Everything is validated on every local rank before any rank takes its
+ * share: all or nothing within the ranks of this process.  Ids of ranks in other processes are checked for range and duplicates
+ * and otherwise ignored (their owner does it).  After pbso_group_finalize. */
+int pbso_group_set_material(pbso_group *g, int n, const int *global_ids, const pbso_material *materials, int keep_state);
 /* ModalSolver::step n_buffers times on every local rank; each engine writes into its slice of the group's gather target
  * (two targets used in turn: the gather of step k runs beside the oscillator bank of step k + 1)                          */
 int pbso_group_step(pbso_group *g, int n_buffers);

@@ -49,6 +49,8 @@ EXPORTS = [
     "pbso_group_read_result", "pbso_shard_by_modes", "pbso_group_scene_mix_enable", "pbso_group_scene_mix_set",
     # force tracks (caller-supplied force signals played by PBSO_TRACK_FORCE messages)
     "pbso_track_create", "pbso_enqueue_track_force", "pbso_track_stats",
+    # retune: a new material for objects of a finalized engine, tables rebuilt on the device
+    "pbso_set_material", "pbso_get_material", "pbso_material_stats", "pbso_group_set_material",
 ]
 STROKE_START, STROKE_END, STROKE_ZERO = 1, 2, 4      # pbso_enqueue_strokes flags
 GATHER_ALL, GATHER_ROOT, GATHER_MIX, GATHER_SCENE, GATHER_FIR = 1, 2, 3, 4, 5
@@ -99,6 +101,11 @@ class TrackPlay(C.Structure):
     """pbso_track_play: which part of which track a PBSO_TRACK_FORCE message plays"""
     _fields_ = [("track", C.c_int), ("loop", C.c_int), ("start_sample", C.c_int), ("reserved", C.c_int),
                 ("n_samples", C.c_int64), ("first", C.c_double), ("rate", C.c_double), ("gain", C.c_double)]
+
+
+class Material(C.Structure):
+    """pbso_material: what pbso_set_material gives an object, 24 bytes"""
+    _fields_ = [("density", C.c_double), ("alpha", C.c_double), ("beta", C.c_double)]
 
 
 class MasterMeter(C.Structure):
@@ -242,6 +249,11 @@ def lib():
         l.pbso_master_window.argtypes = [vp, fp, C.c_size_t]
         l.pbso_master_reset.argtypes = [vp]
         l.pbso_master_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_set_material"):
+        l.pbso_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
+        l.pbso_get_material.argtypes = [vp, C.c_int, C.POINTER(Material)]
+        l.pbso_material_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_group_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
     l.pbso_step_to_host.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     l.pbso_host_wait.argtypes = [vp]
     l.pbso_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]

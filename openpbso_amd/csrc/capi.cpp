@@ -746,6 +746,30 @@ int pbso_write_state(pbso_engine *e, int obj, const double *q1, const double *q2
     GUARD_END(e)
 }
 
+int pbso_set_material(pbso_engine *e, int n, const int *object_ids, const pbso_material *materials, int keep_state) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->set_material(n, object_ids, materials, keep_state);
+    GUARD_END(e)
+}
+
+int pbso_get_material(pbso_engine *e, int object_id, pbso_material *out) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->get_material(object_id, out);
+    GUARD_END(e)
+}
+
+int pbso_material_stats(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    if (!out) return PBSO_ERR_INVALID;
+    GUARD_BEGIN
+    e->impl->material_stats(out);
+    return PBSO_OK;
+    GUARD_END(e)
+}
+
 void *pbso_audio_device_ptr(pbso_engine *e) {
     if (!e || !e->impl) return nullptr;
     return e->impl->audio_ptr();
@@ -779,3 +803,13 @@ int pbso_get_info(pbso_engine *e, pbso_engine_info *out) {
 }
 
 }  // extern "C"
+
+// for the device group (group.cpp): pbso_set_material's validation alone, so that a group call is refused before any rank changes
+namespace pbso {
+int material_check(pbso_engine *e, int n, const int *object_ids, const pbso_material *materials) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->check_material(n, object_ids, materials);
+    GUARD_END(e)
+}
+}  // namespace pbso

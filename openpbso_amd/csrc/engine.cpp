@@ -320,6 +320,9 @@ Engine::~Engine() {
         for (int i = 0; i < 2; ++i) { (void)hipEventDestroy(ev_host_bank_[i]); (void)hipEventDestroy(ev_host_copy_[i]); }
     }
     d_census_.release();
+    h_retune_.release(); d_retune_.release();
+    for (hipEvent_t ev : retune_ev_)
+        if (ev) (void)hipEventDestroy(ev);
     d_scan_.release();
     for (int i = 0; i < N_SETS; ++i) { d_xs_[i].release(); d_xtrow_[i].release(); d_vinc_[i].release(); }
     for (TcSet &ts : tc_) { ts.d_teams.release(); ts.d_split.release(); }
@@ -1866,19 +1869,8 @@ int Engine::listeners_enable(int obj) {
     const Object &o = objs_[obj];
     // this object's f32 operand table (the engine's own table may hold the split-bf16 form)
     std::vector<float> wt((size_t)m_pad_ / 2 * 64, 0.f);
-    for (int m = 0; m < o.n_modes; ++m) {
-        const double eps2 = -o.c2[m], e = (1.0 - o.c1[m]) - o.c2[m];
-        const double a00 = 1.0 - e, a01 = eps2, a10 = -e, a11 = eps2;
-        double p00 = 1, p01 = 0, p10 = 0, p11 = 1;
-        float *w = wt.data() + (size_t)(m / 2) * 64 + 16 * (2 * (m & 1));
-        for (int j = 1; j <= BLOCK_J; ++j) {
-            const double n00 = a00 * p00 + a01 * p10, n01 = a00 * p01 + a01 * p11;
-            const double n10 = a10 * p00 + a11 * p10, n11 = a10 * p01 + a11 * p11;
-            p00 = n00; p01 = n01; p10 = n10; p11 = n11;
-            w[j - 1] = (float)p00;
-            w[16 + j - 1] = (float)p01;
-        }
-    }
+    // (pbso_set_material rebuilds it from the object's new c1 / c2: retune.cpp)
+    for (int m = 0; m < o.n_modes; ++m) mode_walk(o.c1[m], o.c2[m], 0, (size_t)m, 0, W_F32, wt.data(), nullptr, nullptr);
     HIPTRY(hipSetDevice(desc_.device));
     int rc = sync();
     if (rc) return rc;

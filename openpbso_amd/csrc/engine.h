@@ -168,7 +168,9 @@ struct TimedEvent {
 
 struct Object {
     int n_modes = 0;
-    std::vector<double> c1, c2, c3;                      // modal_integrator.h:95-99 (fp64)
+    std::vector<double> c1, c2, c3;                      // modal_integrator.h:95-99 (fp64), of the material in force
+    std::vector<double> omega_squared;                   // the first n_modes eigenvalues as given to add_object: what a new material needs
+    pbso_material material = {0, 0, 0};                  // the one in force (pbso_get_material)
     int n_dof = 0;
     std::vector<double> shapes;                          // mode-major until finalize
     bool have_maps = false;                              // _ffat_maps non-null
@@ -303,6 +305,11 @@ public:
     int read_qnorm(int obj, int buffer, float *out, int n);
     int read_state(int obj, double *q1, double *q2, int n);
     int write_state(int obj, const double *q1, const double *q2, int n);
+    // retune.cpp (kernels_retune.hip): a new material for some objects, their tables rebuilt on the device
+    int set_material(int n, const int *ids, const pbso_material *mats, int keep_state);
+    int check_material(int n, const int *ids, const pbso_material *mats);      // set_material's validation alone: nothing changes
+    int get_material(int obj, pbso_material *out);
+    void material_stats(int64_t out[4]) const;
     void *audio_ptr() { return last_audio_; }
     int read_census(unsigned long long *out, size_t n);
     int info(pbso_engine_info *out);
@@ -338,6 +345,11 @@ private:
     bool valid_obj(int obj) const { return obj >= 0 && obj < (int)objs_.size(); }
     int enqueue_force_impl(int obj, const pbso_force_msg &m, int64_t not_before, const char **why, const pbso_track_play *play = nullptr,
                            int64_t track_total = 0);
+    int64_t retune_calls_ = 0, retune_objects_ = 0, retune_modes_ = 0, retune_g32_ = 0;      // pbso_material_stats
+    PinBuf<unsigned char> h_retune_;                     // a call's upload: [RetuneObj records | (c1, c2, c3) per mode]
+    DevBuf<unsigned char> d_retune_;
+    hipEvent_t retune_ev_[3] = {};                       // PBSO_RETUNE_TIMING=1 (scripts/retune_cost.py): around the two kernels
+    float retune_ms_[2] = {0, 0};
     TrackPool *tracks_ = nullptr;                        // created with the first track
     void track_release();
     int64_t track_length(int track) const;               // -1: no such track
@@ -631,6 +643,9 @@ private:
     double hprof_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};               // PBSO_HOST_PROFILE=1: host milliseconds by stage, printed at destruction
     int64_t last_frows_ = 0, last_trows_ = 0;
 };
+
+// ModalIntegrator<double>::Build + ctor, modal_integrator.h:63-99, for one mode (engine_finalize.cpp); h = 1 / sample rate
+void integrator_coefs(double omega_squared, double density, double alpha, double beta, double h, double &c1, double &c2, double &c3);
 
 // loaders (loaders.cpp)
 int load_modes_file(const char *path, int *n_dof, int *n_modes, std::vector<double> &omega2,

@@ -9,6 +9,26 @@
 
 namespace pbso {
 
+// ModalIntegrator<double>::Build + ctor, modal_integrator.h:63-99: the one copy, for add_object and for pbso_set_material (retune.cpp)
+void integrator_coefs(double omega_squared, double density, double alpha, double beta, double h, double &c1, double &c2, double &c3_out) {
+    const double omega0 = std::sqrt(omega_squared / density);                 // :63
+    const double xi = 0.5 * (alpha / omega0 + beta * omega0);                 // :64
+    const double a = 2.0 * xi * omega0;                                       // :65
+    const double b = std::pow(omega0, 2);                                     // :66
+    const double epsilon = std::exp(-a / 2 * h);                              // :89
+    const double theta = h * std::sqrt(b - a * a / 4.0);                      // :90
+    const double gamma = std::asin(a / (2.0 * std::sqrt(b)));                 // :91
+    const double omega = std::sqrt(b);                                        // :92
+    const double omega_d = std::sqrt(b - std::pow(a, 2) / 4.0);               // :93
+    c1 = 2.0 * epsilon * std::cos(theta);                                     // :95
+    c2 = -std::pow(epsilon, 2);                                               // :96
+    double c3 = 2.0 * (epsilon * std::cos(theta + gamma)
+                       - std::pow(epsilon, 2) * std::cos(2.0 * theta + gamma));  // :97
+    c3 /= (3.0 * omega * omega_d);                                            // :98
+    c3 *= 1E9;                                                                // :99
+    c3_out = c3;
+}
+
 // BuildSolver -> ModalIntegrator<double>::Build + ctor, modal_integrator.h:47-101
 int Engine::add_object(const pbso_object_desc &d, int *id) {
     if (finalized_) return fail(PBSO_ERR_STATE, "add_object after finalize");
@@ -19,25 +39,10 @@ int Engine::add_object(const pbso_object_desc &d, int *id) {
     o.c1.resize(d.n_modes);
     o.c2.resize(d.n_modes);
     o.c3.resize(d.n_modes);
+    o.omega_squared.assign(d.omega_squared, d.omega_squared + d.n_modes);
+    o.material = pbso_material{d.density, d.alpha, d.beta};
     const double h = 1.0 / (double)rate_;
-    for (int ii = 0; ii < d.n_modes; ++ii) {
-        const double omega0 = std::sqrt(d.omega_squared[ii] / d.density);         // :63
-        const double xi = 0.5 * (d.alpha / omega0 + d.beta * omega0);             // :64
-        const double a = 2.0 * xi * omega0;                                       // :65
-        const double b = std::pow(omega0, 2);                                     // :66
-        const double epsilon = std::exp(-a / 2 * h);                              // :89
-        const double theta = h * std::sqrt(b - a * a / 4.0);                      // :90
-        const double gamma = std::asin(a / (2.0 * std::sqrt(b)));                 // :91
-        const double omega = std::sqrt(b);                                        // :92
-        const double omega_d = std::sqrt(b - std::pow(a, 2) / 4.0);               // :93
-        o.c1[ii] = 2.0 * epsilon * std::cos(theta);                               // :95
-        o.c2[ii] = -std::pow(epsilon, 2);                                         // :96
-        double c3 = 2.0 * (epsilon * std::cos(theta + gamma)
-                           - std::pow(epsilon, 2) * std::cos(2.0 * theta + gamma));  // :97
-        c3 /= (3.0 * omega * omega_d);                                            // :98
-        c3 *= 1E9;                                                                // :99
-        o.c3[ii] = c3;
-    }
+    for (int ii = 0; ii < d.n_modes; ++ii) integrator_coefs(d.omega_squared[ii], d.density, d.alpha, d.beta, h, o.c1[ii], o.c2[ii], o.c3[ii]);
     if (d.mode_shapes && d.n_dof > 0) {
         o.n_dof = d.n_dof;
         o.shapes.assign(d.mode_shapes, d.mode_shapes + (size_t)d.n_modes * d.n_dof);

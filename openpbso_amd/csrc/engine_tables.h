@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "mode_tables.h"
 
 namespace pbso {
 
@@ -149,27 +150,8 @@ inline TeamTable build_pipe_table(const std::vector<int> &n_modes) {
 }
 
 // ---- coefficient tables: all in fp64, rounded once ---------------------------------------------------------------------
-// Per mode the one-sample matrix in the basis x = (q, q - q_prev) is A = [[1 - e, eps^2], [-e, eps^2]] (e = 1 - c1 - c2 =
-// |1 - z|^2, eps^2 = -c2; well conditioned at low frequency).
-struct Mat2 {
-    double m00, m01, m10, m11;
-    static Mat2 identity() { return {1, 0, 0, 1}; }
-    static Mat2 step_of(double c1, double c2) {
-        const double eps2 = -c2, e = (1.0 - c1) - c2;
-        return {1.0 - e, eps2, -e, eps2};
-    }
-    Mat2 times(const Mat2 &p) const {                    // this . p
-        return {m00 * p.m00 + m01 * p.m10, m00 * p.m01 + m01 * p.m11, m10 * p.m00 + m11 * p.m10, m10 * p.m01 + m11 * p.m11};
-    }
-    void apply(double &v0, double &v1) const {           // v = this . v
-        const double n0 = m00 * v0 + m01 * v1, n1 = m10 * v0 + m11 * v1;
-        v0 = n0; v1 = n1;
-    }
-    void apply_row(double &r0, double &r1) const {       // r = r . this
-        const double n0 = r0 * m00 + r1 * m10, n1 = r0 * m01 + r1 * m11;
-        r0 = n0; r1 = n1;
-    }
-};
+// The arithmetic per mode (Mat2 and the chains of its powers) lives in mode_tables.h, shared with the kernels that rebuild
+// the tables on the device (pbso_set_material); here are the builders of whole tables, [n_obj][m_pad] planes with zero padding.
 struct ModeCoefs { const double *c1, *c2, *c3; int n_modes; };   // one object (modal_integrator.h:95-99, fp64)
 
 // the oscillator bank's coefficient planes [n_obj][m_pad]
@@ -181,142 +163,53 @@ inline void build_bank_coefs(const std::vector<ModeCoefs> &objs, int m_pad, bool
         const ModeCoefs &o = objs[i];
         for (int m = 0; m < o.n_modes; ++m) {
             const size_t k = i * m_pad + m;
-            if (!direct_form) {
-                ca[k] = (float)(-o.c2[m]);                     // eps^2
-                cb[k] = -(float)((1.0 - o.c1[m]) - o.c2[m]);   // -e, e = |1 - z|^2 = 1 - c1 - c2 (stored negated:
-                                                               //  d = eps^2 d + (-e) q is then a plain v_fmac)
-            } else {
-                ca[k] = (float)o.c1[m];
-                cb[k] = (float)o.c2[m];
-            }
+            mode_bank_coefs(o.c1[m], o.c2[m], direct_form, ca[k], cb[k]);
             c3[k] = o.c3[m];
         }
     }
 }
-// Closed-form qnorm matrices (getQBufferNorm, modal_solver.h:270-273): G = sum_{k=0}^{B-1} (A^k)' e1 e1' A^k per mode (the
-// direct-form kernel forms the difference itself).  Row r_k = e1' A^k: r_{k+1} = r_k A.  Planes G11, 2 G12, G22.
+// Closed-form qnorm matrices (mode_gq): planes G11, 2 G12, G22.
 inline std::vector<float> build_gq_table(const std::vector<ModeCoefs> &objs, int m_pad, int frames) {
     const size_t nm = objs.size() * (size_t)m_pad;
     std::vector<float> gq(3 * nm, 0.f);
     for (size_t i = 0; i < objs.size(); ++i)
-        for (int m = 0; m < objs[i].n_modes; ++m) {
-            const Mat2 a = Mat2::step_of(objs[i].c1[m], objs[i].c2[m]);
-            double r0 = 1.0, r1 = 0.0, s11 = 0.0, s12 = 0.0, s22 = 0.0;
-            for (int k = 0; k < frames; ++k) {
-                s11 += r0 * r0; s12 += r0 * r1; s22 += r1 * r1;
-                a.apply_row(r0, r1);
-            }
-            const size_t k = i * m_pad + m;
-            gq[k] = (float)s11;
-            gq[nm + k] = (float)(2.0 * s12);
-            gq[2 * nm + k] = (float)s22;
-        }
+        for (int m = 0; m < objs[i].n_modes; ++m) mode_gq(objs[i].c1[m], objs[i].c2[m], frames, gq.data() + i * m_pad + m, nm);
     return gq;
 }
-// Block form: row 0 of A^j, j = 1..16, gives the output weights (a_j, b_j); P = A^16 advances the state by one block.
-// P11 is stored as P11 - 1 (q' = q + (P11 - 1) q + P12 d keeps the small angle of low modes).
-// pc: planes P11 - 1, P12, P21, P22; wt: [n_obj * m_pad / 2][64], lane = 16 * (2 * mode-of-pair + comp) + (j - 1).
+// Block form (mode_walk): pc: planes P11 - 1, P12, P21, P22 of P = A^16; wt: [n_obj * m_pad / 2][64], lane = 16 * (2 * mode-of-pair + comp) + (j - 1).
 inline void build_wp_tables(const std::vector<ModeCoefs> &objs, int m_pad, std::vector<float> &pc, std::vector<float> &wt) {
     const size_t nm = objs.size() * (size_t)m_pad;
     pc.assign(4 * nm, 0.f);
     wt.assign(nm / 2 * 64, 0.f);
     for (size_t i = 0; i < objs.size(); ++i)
-        for (int m = 0; m < objs[i].n_modes; ++m) {
-            const Mat2 a = Mat2::step_of(objs[i].c1[m], objs[i].c2[m]);
-            Mat2 p = Mat2::identity();                                 // A^j
-            const size_t k = i * m_pad + m;
-            float *w = wt.data() + (k / 2) * 64 + 16 * (2 * (k & 1));
-            for (int j = 1; j <= BLOCK_J; ++j) {
-                p = a.times(p);
-                w[j - 1] = (float)p.m00;
-                w[16 + j - 1] = (float)p.m01;
-            }
-            pc[k] = (float)(p.m00 - 1.0);
-            pc[nm + k] = (float)p.m01;
-            pc[2 * nm + k] = (float)p.m10;
-            pc[3 * nm + k] = (float)p.m11;
-        }
+        for (int m = 0; m < objs[i].n_modes; ++m)
+            mode_walk(objs[i].c1[m], objs[i].c2[m], 0, i * m_pad + m, nm, W_F32, wt.data(), pc.data(), nullptr);
 }
-// K5: a whole buffer as one step of the state -- A^B (first entry minus one, as P) and A^(B-1) u, u = (1, 1)': what a
-// force sample at the buffer's first sample leaves at its end.  6 planes.
+// K5 (mode_walk): A^B (first entry minus one, as P) and A^(B-1) u.  6 planes.
 inline std::vector<float> build_scan_table(const std::vector<ModeCoefs> &objs, int m_pad, int frames) {
     const size_t nm = objs.size() * (size_t)m_pad;
     std::vector<float> sc(6 * nm, 0.f);
     for (size_t i = 0; i < objs.size(); ++i)
-        for (int m = 0; m < objs[i].n_modes; ++m) {
-            const Mat2 a = Mat2::step_of(objs[i].c1[m], objs[i].c2[m]);
-            Mat2 p = Mat2::identity();
-            const size_t k = i * m_pad + m;
-            for (int j = 1; j <= frames; ++j) {
-                if (j == frames) {                               // A^(B-1) u
-                    sc[4 * nm + k] = (float)(p.m00 + p.m01);
-                    sc[5 * nm + k] = (float)(p.m10 + p.m11);
-                }
-                p = a.times(p);
-            }
-            sc[k] = (float)(p.m00 - 1.0);
-            sc[nm + k] = (float)p.m01;
-            sc[2 * nm + k] = (float)p.m10;
-            sc[3 * nm + k] = (float)p.m11;
-        }
+        for (int m = 0; m < objs[i].n_modes; ++m)
+            mode_walk(objs[i].c1[m], objs[i].c2[m], frames, i * m_pad + m, nm, W_NONE, nullptr, nullptr, sc.data());
     return sc;
 }
-// Forced block path without qnorm rows (kernels_block.hip, FT): a force sample f enters the state as f u, u = (1, 1)'
-// (d += f, q += d), so the samples 16 n + i, i = 1..16, of a dense profile move the next block-start state by
-// sum_i A^(16 - i) u f_i.  Plane 2 i' + c holds component c of A^(15 - i') u, i' = 0..15, per mode.
+// Forced block path without qnorm rows (mode_ftab): plane 2 i' + c holds component c of A^(15 - i') u, i' = 0..15, per mode.
 inline std::vector<float> build_f_table(const std::vector<ModeCoefs> &objs, int m_pad) {
     const size_t nm = objs.size() * (size_t)m_pad;
     std::vector<float> ft((size_t)32 * nm, 0.f);
     for (size_t i = 0; i < objs.size(); ++i)
-        for (int m = 0; m < objs[i].n_modes; ++m) {
-            const Mat2 a = Mat2::step_of(objs[i].c1[m], objs[i].c2[m]);
-            double v0 = 1.0, v1 = 1.0;                              // A^delta u, delta = 0, 1, ...
-            const size_t k = i * m_pad + m;
-            for (int delta = 0; delta < BLOCK_J; ++delta) {
-                const int ip = BLOCK_J - 1 - delta;                // in-block sample index (0-based) this power belongs to
-                ft[(size_t)(2 * ip) * nm + k] = (float)v0;
-                ft[(size_t)(2 * ip + 1) * nm + k] = (float)v1;
-                a.apply(v0, v1);
-            }
-        }
+        for (int m = 0; m < objs[i].n_modes; ++m) mode_ftab(objs[i].c1[m], objs[i].c2[m], i * m_pad + m, nm, ft.data());
     return ft;
 }
-// hi = bf16(x) round-to-nearest-even, lo = bf16(x - hi)
-inline uint32_t bf16_rne(float x) {
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u) return u >> 16;                 // inf / nan
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-inline void bf16_split(double x, uint32_t &hi, uint32_t &lo) {
-    const float xf = (float)x;
-    hi = bf16_rne(xf);
-    const uint32_t hb = hi << 16;
-    float hf;
-    std::memcpy(&hf, &hb, 4);
-    lo = bf16_rne(xf - hf);
-}
-// Split-bf16 operand table from the f32 W table, in place: per group of 16 columns 8 rows of 64 dwords, rows 0..3 the hi
-// parts, 4..7 the lo parts; lane l = 16 kq + (j - 1), dword dd <-> mode 16 G + 4 kq + dd: low half a_j, high half b_j (the k
-// order of v_mfma_f32_16x16x32_bf16: k = 8 kq + 2 dd + comp).
+// Split-bf16 operand table from the f32 W table, in place (layouts: mode_tables.h, wtab_f32_index / wtab_bf16_index).
 inline void wtab_to_split_bf16(std::vector<float> &wt, size_t nm) {
     const std::vector<float> wf(wt);
     std::vector<uint32_t> w16(wt.size(), 0u);
-    for (size_t G = 0; G < nm / 16; ++G)
-        for (int l = 0; l < 64; ++l) {
-            const int j = l & 15, kq = l >> 4;
-            for (int dd = 0; dd < 4; ++dd) {
-                const size_t col = 16 * G + 4 * kq + dd;                      // flat column index (object * m_pad + column)
-                // f32 table: row col / 2, lane 16 * (2 * (col & 1) + comp) + j
-                const float a = wf[(col / 2) * 64 + 16 * (2 * (col & 1) + 0) + j];
-                const float b = wf[(col / 2) * 64 + 16 * (2 * (col & 1) + 1) + j];
-                uint32_t ah, al, bh, bl;
-                bf16_split((double)a * TRUNC_SPLIT_GAIN, ah, al);
-                bf16_split((double)b * TRUNC_SPLIT_GAIN, bh, bl);
-                w16[(8 * G + dd) * 64 + l] = ah | (bh << 16);
-                w16[(8 * G + 4 + dd) * 64 + l] = al | (bl << 16);
-            }
-        }
+    for (size_t col = 0; col < nm / 16 * 16; ++col)                           // flat column index (object * m_pad + column)
+        for (int j = 0; j < BLOCK_J; ++j)
+            split_bf16_pair(wf[wtab_f32_index(col, 0, j)], wf[wtab_f32_index(col, 1, j)], w16[wtab_bf16_index(col, 0, j)],
+                            w16[wtab_bf16_index(col, 1, j)]);
     std::memcpy(wt.data(), w16.data(), wt.size() * sizeof(float));
 }
 
@@ -329,7 +222,7 @@ inline void transpose_shapes(const std::vector<double> &shapes, const double *c3
         for (int dof = 0; dof < n_dof; ++dof) {
             const double u = shapes[(size_t)m * n_dof + dof];
             vm[(size_t)dof * m_pad + m] = u;
-            vg[(size_t)dof * m_pad + m] = (float)(c3[m] * u);
+            vg[(size_t)dof * m_pad + m] = mode_g32(c3[m], u);
         }
 }
 

@@ -16,6 +16,11 @@
 #include "../../include/openpbso_amd.h"
 #include "kernels.h"
 
+namespace pbso {
+// capi.cpp: pbso_set_material's validation alone (nothing changes)
+int material_check(pbso_engine *e, int n, const int *object_ids, const pbso_material *materials);
+}  // namespace pbso
+
 namespace {
 
 // ---- the part of RCCL's C API this file calls (rccl/rccl.h; the values are NCCL's ABI)
@@ -451,6 +456,30 @@ int pbso_group_enqueue_force(pbso_group *g, int id, const pbso_force_msg *m, int
     int took = pbso_enqueue_force(rk->eng, l, m, not_before);
     if (took < 0) return gfail(g, took, pbso_last_error(rk->eng));
     return took;
+}
+
+int pbso_group_set_material(pbso_group *g, int n, const int *ids, const pbso_material *mats, int keep_state) {
+    if (!g || !g->finalized) return gfail(g, PBSO_ERR_STATE, "set_material before finalize");
+    if (n < 0 || (n > 0 && (!ids || !mats))) return gfail(g, PBSO_ERR_INVALID, "set_material arguments");
+    // every rank's share, in call order; then all of them checked before the first one is taken
+    std::vector<std::vector<int>> lid(g->ranks.size());
+    std::vector<std::vector<pbso_material>> lmat(g->ranks.size());
+    std::vector<unsigned char> named(g->n_objects, 0);
+    for (int i = 0; i < n; ++i) {
+        int r = 0, l = 0;
+        int rc = pbso_group_owner(g, ids[i], &r, &l);
+        if (rc != PBSO_OK) return gfail(g, PBSO_ERR_INVALID, "set_material: object id out of range");
+        if (named[ids[i]]) return gfail(g, PBSO_ERR_INVALID, "set_material: an object id is named twice");
+        named[ids[i]] = 1;
+        if (!local_rank(g, r)) continue;                  // its owner does it
+        lid[r - g->first].push_back(l);
+        lmat[r - g->first].push_back(mats[i]);
+    }
+    for (size_t k = 0; k < g->ranks.size(); ++k)
+        if (!lid[k].empty()) GENG(g, g->ranks[k], pbso::material_check(g->ranks[k].eng, (int)lid[k].size(), lid[k].data(), lmat[k].data()));
+    for (size_t k = 0; k < g->ranks.size(); ++k)
+        if (!lid[k].empty()) GENG(g, g->ranks[k], pbso_set_material(g->ranks[k].eng, (int)lid[k].size(), lid[k].data(), lmat[k].data(), keep_state));
+    return PBSO_OK;
 }
 
 int pbso_group_step(pbso_group *g, int nb) {

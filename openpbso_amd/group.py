@@ -124,6 +124,13 @@ class Group:
     def enqueue_force(self, global_id, msg, not_before=0):
         return bool(self._chk(self._l.pbso_group_enqueue_force(self._h, global_id, C.byref(msg.to_c()), not_before)))
 
+    def set_material(self, global_ids, density, alpha, beta, keep_state=True):
+        """pbso_group_set_material: Engine.set_material on the owners of the ids, all or nothing within this process"""
+        from .solver import material_array
+        mats = material_array(global_ids, density, alpha, beta)
+        gid = np.ascontiguousarray(np.atleast_1d(global_ids), dtype=np.int32)
+        self._chk(self._l.pbso_group_set_material(self._h, gid.size, gid.ctypes.data_as(C.POINTER(C.c_int)), mats, int(bool(keep_state))))
+
     # -- stepping -----------------------------------------------------------------
     def step(self, n_buffers):
         self._chk(self._l.pbso_group_step(self._h, n_buffers))

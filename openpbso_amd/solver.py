@@ -85,6 +85,16 @@ class ForceMessage:
         return m
 
 
+def material_array(ids, density, alpha, beta):
+    """an array of capi.Material, one per id; scalars broadcast over the ids"""
+    n = np.atleast_1d(ids).size
+    d, a, b = (np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in (density, alpha, beta))
+    mats = (capi.Material * max(n, 1))()
+    for i in range(n):
+        mats[i].density, mats[i].alpha, mats[i].beta = float(d[i]), float(a[i]), float(b[i])
+    return mats
+
+
 def _select_from_env():
     """Test / A-B convenience of THIS wrapper (the library reads no such variables): the kernel- and path-selection fields of
     pbso_engine_desc (ABI 4) from the environment, so that a whole pytest / bench run can pin one path.
@@ -548,6 +558,25 @@ class Engine:
         b = np.ascontiguousarray(q2, dtype=np.float64)
         assert a.size == b.size
         self._chk(self._l.pbso_write_state(self._h, obj, _dp(a), _dp(b), a.size))
+
+    def set_material(self, ids, density, alpha, beta, keep_state=True):
+        """pbso_set_material: a new material for the objects `ids` of a finalized engine, in force from the next step's first
+        sample; scalars broadcast over the ids.  keep_state: the state carries on (True) or is zeroed (False)."""
+        mats = material_array(ids, density, alpha, beta)
+        oid = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        self._chk(self._l.pbso_set_material(self._h, oid.size, oid.ctypes.data_as(C.POINTER(C.c_int)), mats, int(bool(keep_state))))
+
+    def material(self, obj):
+        """pbso_get_material: (density, alpha, beta) in force for an object"""
+        m = capi.Material()
+        self._chk(self._l.pbso_get_material(self._h, int(obj), C.byref(m)))
+        return m.density, m.alpha, m.beta
+
+    def material_stats(self):
+        """pbso_material_stats: calls accepted, objects retuned, modes rebuilt, g32 elements rebuilt"""
+        out = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_material_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def census(self, n_teams=None):
         """per-workgroup (start, end [100 MHz ticks], HW_ID, XCC_ID, clock start/end, block form: cycles in head / pipeline / barrier / combine) of the last launch (PBSO_CENSUS=1).

@@ -53,6 +53,11 @@
 //                    the file has the length and alignment of the run without --limit.  --pcm16 writes a 16-bit PCM WAV (format 1)
 //                    converted on the device (pbso_read_master_pcm16); only with --limit.  One engine only: not with --devices;
 //                    not with --raw (the unscaled mix).
+//   --retune FILE    materials changed during the run (pbso_set_material; with --devices pbso_group_set_material): lines
+//                    <buffer> <copy> <material file> [keep|zero] give copy the file's material (the format of -t) from that
+//                    buffer on; keep (the default): the state carries on under the new coefficients, zero: it is cleared.  Every
+//                    distinct path is loaded once.  The run is cut at these buffers as --pan cuts it; composes with --copies,
+//                    --channels and --limit.  The mode count stays the one of the -t material.
 #include <dirent.h>
 
 #include <algorithm>
@@ -267,10 +272,72 @@ struct Scene {
     }
 };
 
+// --retune: the material script.  Lines <buffer> <copy> <material file> [keep|zero]: from that buffer on the copy has the file's
+// material (pbso_set_material; keep, the default: the state carries on, zero: it is cleared).  The run is cut at these buffers.
+struct RetuneLine { long b; int copy, file; bool keep; };
+struct RetuneScript {
+    std::vector<RetuneLine> lines;
+    std::vector<std::string> paths;                      // every distinct material file, loaded once
+    std::vector<pbso_material> materials;
+    bool empty() const { return lines.empty(); }
+    void read(const std::string &path, int copies, int n_buffers) {
+        std::ifstream f(path);
+        if (!f) die("cannot read " + path);
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            RetuneLine p;
+            std::string file, word;
+            if (!(iss >> p.b >> p.copy >> file)) die("bad retune line (<buffer> <copy> <material file> [keep|zero]): " + line);
+            p.keep = true;
+            if (iss >> word) {
+                if (word == "zero") p.keep = false;
+                else if (word != "keep") die("bad retune line (keep or zero): " + line);
+            }
+            if (p.copy < 0 || p.copy >= copies) die("retune line for a copy that does not exist: " + line);
+            if (p.b < 0 || p.b >= n_buffers) die("retune line outside buffers 0 .. --buffers - 1: " + line);
+            p.file = (int)(std::find(paths.begin(), paths.end(), file) - paths.begin());
+            if (p.file == (int)paths.size()) {
+                double mat[5];
+                if (pbso_material_read(file.c_str(), mat) != PBSO_OK) die("cannot read material file " + file);
+                paths.push_back(file);
+                materials.push_back(pbso_material{mat[0], mat[3], mat[4]});
+            }
+            lines.push_back(p);
+        }
+        if (lines.empty()) die("no lines in " + path);
+    }
+    // the change points merged into a list of cuts (sorted, unique; the last entry stays the end of the run)
+    std::vector<int> cut(std::vector<int> cuts, int n_buffers) const {
+        for (const RetuneLine &p : lines)
+            if (p.b > 0 && p.b < n_buffers) cuts.push_back((int)p.b);
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        return cuts;
+    }
+    // the lines of buffer b as one call per keep / zero: set(n, copies, materials, keep_state)
+    template <class Set>
+    void apply_at(long b, Set set) const {
+        for (int keep = 1; keep >= 0; --keep) {
+            std::vector<int> ids;
+            std::vector<pbso_material> mats;
+            for (const RetuneLine &p : lines)
+                if (p.b == b && p.keep == (keep != 0)) {
+                    // (a copy named twice at one buffer: the later line wins, as a later buffer's would)
+                    auto at = std::find(ids.begin(), ids.end(), p.copy);
+                    if (at != ids.end()) mats[at - ids.begin()] = materials[p.file];
+                    else { ids.push_back(p.copy); mats.push_back(materials[p.file]); }
+                }
+            if (!ids.empty()) set((int)ids.size(), ids.data(), mats.data(), keep);
+        }
+    }
+};
+
 // the scene on several GPUs (include/openpbso_amd.h "device group")
 static int run_group(const std::vector<int> &devices, int copies, int shift, const std::string &modes, const std::string &material,
                      const std::string &ffat, const std::vector<Hit> &hits, const std::vector<std::vector<float>> &tracks,
-                     const std::vector<Pos> &path, const StrokeScript &strokes, int n_buffers, const Scene *scene, std::vector<float> &sound) {
+                     const std::vector<Pos> &path, const StrokeScript &strokes, int n_buffers, const Scene *scene, const RetuneScript &retune, std::vector<float> &sound) {
     auto gcheck = [](pbso_group *g, int rc, const char *what) {
         if (rc < 0) die(std::string(what) + ": " + pbso_status_string(rc) + ": " + (g ? pbso_group_last_error(g) : ""));
     };
@@ -348,6 +415,9 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         for (size_t r = 0; r < devices.size(); ++r)
             if (!rank_ids[r].empty()) feed_strokes(pbso_group_engine(g, (int)r), strokes, rank_ids[r], rank_shift[r], b0, b1, feeds[r]);
     };
+    auto group_set = [&](int n, const int *ids, const pbso_material *mats, int keep) {
+        gcheck(g, pbso_group_set_material(g, n, ids, mats, keep), "group_set_material");
+    };
     if (scene) {
         // the segments between the pan script's change points, each gathered as a C-channel scene mix: sound [C][n_buffers * B]
         const int C = scene->channels;
@@ -361,8 +431,9 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         std::vector<float> taps(scene->fir ? (size_t)C * copies * scene->n_taps : 0, 0.f);
         std::vector<int> onset(copies, 0);
         sound.assign((size_t)C * total, 0.f);
-        const std::vector<int> cuts = scene->cuts(n_buffers);
+        const std::vector<int> cuts = retune.cut(scene->cuts(n_buffers), n_buffers);
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+            retune.apply_at(cuts[k], group_set);
             if (scene->fir) {
                 if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
                 if (scene->fir_delay_set_at(cuts[k], fir_delay)) gcheck(g, pbso_group_scene_fir_set_delay(g, fir_delay.data()), "group_scene_fir_set_delay");
@@ -379,11 +450,17 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
                           sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
         }
     } else {
-        feed_ranks(0, n_buffers);
-        gcheck(g, pbso_group_step(g, n_buffers), "group_step");
-        gcheck(g, pbso_group_gather(g, PBSO_GATHER_MIX), "group_gather");
+        // (one step; with --retune the segments between its change points, each gathered as the on-device mix)
         sound.resize((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
-        gcheck(g, pbso_group_read_result(g, 0, sound.data(), sound.size()), "group_read_result");
+        const std::vector<int> cuts = retune.cut({0, n_buffers}, n_buffers);
+        for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+            retune.apply_at(cuts[k], group_set);
+            feed_ranks(cuts[k], cuts[k + 1]);
+            gcheck(g, pbso_group_step(g, cuts[k + 1] - cuts[k]), "group_step");
+            gcheck(g, pbso_group_gather(g, PBSO_GATHER_MIX), "group_gather");
+            gcheck(g, pbso_group_read_result(g, 0, sound.data() + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER,
+                                             (size_t)(cuts[k + 1] - cuts[k]) * PBSO_FRAMES_PER_BUFFER), "group_read_result");
+        }
     }
     std::printf("%d copies x %d audible modes on %d device(s): ranks own", copies, n_aud, (int)devices.size());
     for (int r = 0; r < (int)devices.size(); ++r) {
@@ -397,7 +474,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_delay, reverb, strokes_file, arprm_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_delay, reverb, strokes_file, arprm_arg, retune_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1;
     Scene scene;
@@ -432,6 +509,7 @@ int main(int argc, char **argv) {
         else if (a == "--copy-shift") copy_shift = std::atoi(val().c_str());
         else if (a == "--channels") scene.channels = std::atoi(val().c_str());
         else if (a == "--pan") pan = val();
+        else if (a == "--retune") retune_arg = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else if (a == "--fir") fir = val();
         else if (a == "--fir-delay") fir_delay = val();
@@ -625,6 +703,8 @@ int main(int argc, char **argv) {
         if (devices.empty()) die("--devices needs a list of HIP ordinals");
         if (copies <= 0) copies = (int)devices.size();
     }
+    RetuneScript retune;
+    if (!retune_arg.empty()) retune.read(retune_arg, devices.empty() ? 1 : copies, n_buffers);
     const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
     if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
     if (!fir_delay.empty() && fir.empty()) die("--fir-delay needs --fir FILE: the delay sits in front of the filter mix");
@@ -730,7 +810,7 @@ int main(int argc, char **argv) {
     std::vector<int16_t> pcm;                            // --pcm16: the master bus's frames, interleaved, segment behind segment
     double device_ms = 0;
     if (!devices.empty()) {
-        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, sound);
+        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, retune, sound);
     } else {
         pbso_engine_desc desc;
         std::memset(&desc, 0, sizeof(desc));
@@ -780,6 +860,9 @@ int main(int argc, char **argv) {
                 check(e, pbso_read_master(e, seg.data(), seg.size()), "read_master");
             }
         };
+        auto engine_set = [&](int n, const int *ids, const pbso_material *mats, int keep) {
+            check(e, pbso_set_material(e, n, ids, mats, keep), "set_material");      // (one object: copy 0 is object 0)
+        };
         if (mixed) {
             // the one object through the scene mixer, segment by segment: sound [C][n_buffers * B]
             const int C = scene.channels;
@@ -802,9 +885,10 @@ int main(int argc, char **argv) {
                 check(e, pbso_scene_reverb_enable(e, 1, C, scene.reverb_taps, scene.reverb_xfade), "scene_reverb_enable");
                 check(e, pbso_scene_reverb_set(e, scene.reverb.data()), "scene_reverb_set");
             }
-            std::vector<int> cuts = scene.cuts(n_buffers);
+            std::vector<int> cuts = retune.cut(scene.cuts(n_buffers), n_buffers);
             if (n_tail) cuts.push_back(n_run);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+                if (cuts[k] < n_buffers) retune.apply_at(cuts[k], engine_set);
                 if (cuts[k] >= n_buffers) {
                     // (--limit's tail: the script ended with the run)
                 } else if (scene.fir) {
@@ -837,10 +921,26 @@ int main(int argc, char **argv) {
             pbso_host_free(bus);
         } else {
             sound.resize((size_t)n_run * PBSO_FRAMES_PER_BUFFER);
-            feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
-            check(e, pbso_step(e, n_run), "step");
-            check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
-            if (limit) master_segment(sound);
+            if (retune.empty()) {
+                feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
+                check(e, pbso_step(e, n_run), "step");
+                check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
+                if (limit) master_segment(sound);
+            } else {
+                // the segments between the material script's change points (--limit's tail behind the last one)
+                std::vector<int> cuts = retune.cut({0, n_buffers}, n_buffers);
+                cuts.back() = n_run;
+                std::vector<float> seg;
+                for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+                    retune.apply_at(cuts[k], engine_set);
+                    feed_strokes(e, strokes, stroke_ids, stroke_shift, cuts[k], std::min(cuts[k + 1], n_buffers), feed);
+                    check(e, pbso_step(e, cuts[k + 1] - cuts[k]), "step");
+                    seg.resize((size_t)(cuts[k + 1] - cuts[k]) * PBSO_FRAMES_PER_BUFFER);
+                    check(e, pbso_read_audio(e, seg.data(), seg.size()), "read_audio");
+                    if (limit) master_segment(seg);
+                    std::copy(seg.begin(), seg.end(), sound.begin() + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
+                }
+            }
         }
         if (limit) check(e, pbso_sync(e), "sync");
         pbso_host_free(m_in);
