@@ -355,6 +355,15 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
         asm volatile("" : "+v"(v));
         return v;
     };
+    // A per-lane access inside the buffer loop is a uniform base (an SGPR pair; buffer rows and planes are scalar adds) + the lane's
+    // BYTE offset, 32 bits, slice r at + r * rowlen4: the saddr form of global_load_dword / global_store_dword, no 64-bit address
+    // built on the vector ALU per access (it shares its datapath with the SIMD partner's MFMAs).  The slice's step is part of the
+    // 32-bit offset -- one v_add_u32 per slice and site: as a step of the BASE the compiler adds the lane offset to the array
+    // first and the steps, hoisted out of the loop, behind it: three 64-bit vector adds per array and slice again.
+    const unsigned rowlen4 = 4u * rowlen;
+    auto lane_off4 = [&]() { return 4u * lane_off(); };
+    auto ld_row = [](const float *base, unsigned off) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off); };
+    auto st_row = [](float *base, unsigned off, float v) { *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v; };
     // DUMP: xdump[row][qn_nb][32 blocks][m_pad] pairs (Q, D), xscale[row][qn_nb][m_pad] (0 marks a buffer that was
     // stepped per sample: no block states)
     const int dump_row = DUMP ? p_dump_row[obj] : -1;
@@ -370,9 +379,9 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
     auto dump_scale = [&](int code) {
         if (DUMP && dump_row >= 0) {
             float *dst = p_xscale + ((size_t)dump_row * p.qn_nb + dump_b) * p.m_pad + team.col0;
-            const unsigned utid = lane_off();
+            const unsigned off = lane_off4();
 #pragma unroll
-            for (int r = 0; r < R; ++r) dst[r * rowlen + utid] = code > 0 ? t[r] : (float)code;
+            for (int r = 0; r < R; ++r) st_row(dst, off + r * rowlen4, code > 0 ? t[r] : (float)code);
         }
     };
     // (the qnorm matrices are a fetch of their own: in the f32 pipeline they are requested BEHIND the last matrix burst, when its
@@ -380,34 +389,33 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
     //  barrier and the combine)
     auto prefetch_gq = [&]() {
         if (QN) {
-            const unsigned utid = lane_off();
+            const unsigned off = lane_off4();
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const unsigned k = r * rowlen + utid;
-                ng11[r] = b_gq[k];
-                ng12[r] = (b_gq + p.plane)[k];
-                ng22[r] = (b_gq + 2 * p.plane)[k];
+                ng11[r] = ld_row(b_gq, off + r * rowlen4);
+                ng12[r] = ld_row(b_gq + p.plane, off + r * rowlen4);
+                ng22[r] = ld_row(b_gq + 2 * p.plane, off + r * rowlen4);
             }
         }
     };
     auto prefetch = [&](const BufDesc &nd, bool with_gq = true) {
-        const unsigned utid = lane_off();
+        const unsigned off = lane_off4();
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const unsigned k = r * rowlen + utid;
-            nca[r] = b_ca[k];
-            ncb[r] = b_cb[k];
+            nca[r] = ld_row(b_ca, off + r * rowlen4);
+            ncb[r] = ld_row(b_cb, off + r * rowlen4);
         }
         if (with_gq) prefetch_gq();
         if (nd.frow >= 0 && !(nd.flags & DESC_DIRECT)) {
             const float *__restrict__ gsrc = p_grows + (size_t)nd.frow * p.m_pad + team.col0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) ngr[r] = gsrc[r * rowlen + utid];
+            for (int r = 0; r < R; ++r) ngr[r] = ld_row(gsrc, off + r * rowlen4);
         }
         if (nd.trow >= 0) {
             const double *__restrict__ tsrc = p_xfer_rows + (size_t)nd.trow * p.m_pad + team.col0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) ntr[r] = (float)tsrc[r * rowlen + utid];     // (fp64 rows: the FFAT kernel is bit-exact with the oracle)
+            for (int r = 0; r < R; ++r)                                                // (fp64 rows: the FFAT kernel is bit-exact with the oracle)
+                ntr[r] = (float)*reinterpret_cast<const double *>(reinterpret_cast<const char *>(tsrc) + 2u * (off + r * rowlen4));
         }
     };
 
@@ -573,11 +581,11 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
         if (flags & DESC_SKIP) {
             dump_scale(-1);
             // the reference's step() returned before stepping: no samples, state untouched
-            for (int i = tid; i < B; i += blockDim.x) aout[(size_t)b * B + i] = 0.f;
+            const unsigned off = lane_off4();
+            for (unsigned o = off; o < 4u * (unsigned)B; o += rowlen4) st_row(aout + (size_t)b * B, o, 0.f);
             if (QN) {
-                const unsigned utid = lane_off();
 #pragma unroll
-                for (int r = 0; r < R; ++r) (b_qn + (size_t)b * p.m_pad)[r * rowlen + utid] = 0.f;
+                for (int r = 0; r < R; ++r) st_row(b_qn + (size_t)b * p.m_pad, off + r * rowlen4, 0.f);
             }
             prefetch(next);
             prefetch_direct(next);
@@ -630,7 +638,7 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
             }
             if (QN) {
                 // sum_{k=0}^{B-1} q_k^2 = x0' G x0, x0 = state after sample 0 (the rest of the buffer is force-free)
-                const unsigned utid = lane_off();
+                const unsigned off = lane_off4();
 #pragma unroll
                 for (int v = 0; v < R; ++v) {
                     float e = ng22[v] * x2[v].y * x2[v].y;
@@ -638,7 +646,7 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                     e = fmaf(ng11[v] * x2[v].x, x2[v].x, e);
                     // v_sqrt_f32 / v_rcp_f32 (1 ulp each): the closed form itself is good to ~1e-5 only
                     const float nrm = __builtin_amdgcn_sqrtf(fmaxf(e, 0.f));     // (it can round a tiny sum below zero)
-                    (b_qn + (size_t)b * p.m_pad)[v * rowlen + utid] = nrm * __builtin_amdgcn_rcpf(t[v]);
+                    st_row(b_qn + (size_t)b * p.m_pad, off + v * rowlen4, nrm * __builtin_amdgcn_rcpf(t[v]));
                 }
             }
             p0 = wave_sum(p0);
@@ -1074,9 +1082,9 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                 combine_half(grp);
             });
             if (QN) {
-                const unsigned utid = lane_off();
+                const unsigned off = lane_off4();
 #pragma unroll
-                for (int r = 0; r < R; ++r) (b_qn + (size_t)b * p.m_pad)[r * rowlen + utid] = sqrtf(qn[r]) / t[r];
+                for (int r = 0; r < R; ++r) st_row(b_qn + (size_t)b * p.m_pad, off + r * rowlen4, sqrtf(qn[r]) / t[r]);
             }
             prefetch(next);
             }
@@ -1131,11 +1139,11 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
                 if (HALF && (c % BN) == BN - 1) combine_half(c / BN);
             }
             if (QN) {
-                const unsigned utid = lane_off();
+                const unsigned off = lane_off4();
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const float nrm = sqrtf(qn[r]);
-                    (b_qn + (size_t)b * p.m_pad)[r * rowlen + utid] = scaled ? nrm / t[r] : nrm;
+                    st_row(b_qn + (size_t)b * p.m_pad, off + r * rowlen4, scaled ? nrm / t[r] : nrm);
                 }
             }
             prefetch(next);                            // (not hidden here: literal buffers are the slow path anyway)
@@ -1153,18 +1161,25 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
             float *__restrict__ ao = aout + (size_t)b * B;
             // (the thread index laundered: otherwise LICM keeps the ring address of thread j alive across the whole pipeline, and
             //  the headline build, which has no register to spare, spills it)
+            // Sample 0 rides along: every thread reads the waves' entries (one address: a broadcast) in the same pass as its four
+            // block sums -- one wait per wave for both, in the order w = 0 .. W - 1 as before -- and thread 0 stores it with the rest
+            // (as a chain of its own behind the loop, thread 0 read, waited and added once per wave before its wave went on).
             for (int j = (int)lane_off(); j < GROUP * NG / 4; j += blockDim.x) {
                 f4 acc = *reinterpret_cast<const f4 *>(r0 + 4 * j);
-                for (int w = 1; w < W; ++w) acc += *reinterpret_cast<const f4 *>(r0 + w * WAVE_FLOATS + 4 * j);
-                AUDIO_STORE(&ao[4 * j + 1], acc.x);
-                AUDIO_STORE(&ao[4 * j + 2], acc.y);
-                AUDIO_STORE(&ao[4 * j + 3], acc.z);
-                AUDIO_STORE(&ao[4 * j + 4], acc.w);
-            }
-            if (tid == 0) {
-                float acc = r0[GROUP * NG];
-                for (int w = 1; w < W; ++w) acc += r0[w * WAVE_FLOATS + GROUP * NG];
-                AUDIO_STORE(&ao[0], acc);
+                float a0 = r0[GROUP * NG];
+                for (int w = 1; w < W; ++w) {
+                    const f4 v = *reinterpret_cast<const f4 *>(r0 + w * WAVE_FLOATS + 4 * j);
+                    const float v0 = r0[w * WAVE_FLOATS + GROUP * NG];
+                    __builtin_amdgcn_sched_barrier(0);          // (both reads before the adds: one wait)
+                    acc += v;
+                    a0 += v0;
+                }
+                float *__restrict__ aj = reinterpret_cast<float *>(reinterpret_cast<char *>(ao) + 16u * (unsigned)j);
+                AUDIO_STORE(&aj[1], acc.x);
+                AUDIO_STORE(&aj[2], acc.y);
+                AUDIO_STORE(&aj[3], acc.z);
+                AUDIO_STORE(&aj[4], acc.w);
+                if (j == 0) AUDIO_STORE(&ao[0], a0);
             }
         }
         lap(cy_comb);
