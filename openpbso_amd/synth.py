@@ -78,7 +78,9 @@ def ffat_maps(lam, seed, dim=16, cell_size=0.01, center=(0.0, 0.0, 0.0)):
 
 def listener_path(n_buffers, radius=0.5, steps_per_turn=86):
     """Circle of `radius` in a plane tilted off every axis (no zero direction
-    component: SURVEY Q10), one position per buffer."""
+    component: SURVEY Q10), one position per buffer.  Listeners ON an axis, on
+    the diagonals and inside the map's box are the business of
+    tests/ffat_boxes.py (edge_positions) and tests/test_gpu_ffat_boxes.py."""
     a = 2 * np.pi * np.arange(n_buffers) / steps_per_turn + 0.1234
     e1 = np.array([1.0, 0.35, 0.2])
     e1 /= np.linalg.norm(e1)

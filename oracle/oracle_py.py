@@ -239,6 +239,34 @@ def uniform_cube(mode_id, k, center, cell_size, dim, psi):
     return m
 
 
+def ffat_map(m):
+    """An OrFfatMap with the runtime fields of the dict `m` copied in (the keys of synth.uniform_cube_geometry plus mode_id, k,
+    psi): any box, the general sibling of uniform_cube.  psi is borrowed, not copied: the array is kept alive on the struct,
+    which therefore must not be handed to or_ffat_free."""
+    om = OrFfatMap()
+    om.mode_id = int(m["mode_id"])
+    om.k = float(m["k"])
+    om.is_compressed = 0
+    om.cell_size = float(m["cell_size"])
+    for j in range(3):
+        om.center3[j] = float(m["center3"][j])
+        om.center[j] = float(m["center"][j])
+        om.bbox_low[j] = float(m["bbox_low"][j])
+        om.bbox_top[j] = float(m["bbox_top"][j])
+    for f in range(6):
+        for j in range(3):
+            om.low_corners[f][j] = float(m["low_corners"][f][j])
+        om.n_elements[f][0] = int(m["n_elements"][f][0])
+        om.n_elements[f][1] = int(m["n_elements"][f][1])
+        om.strides[f] = int(m["strides"][f])
+    psi = np.ascontiguousarray(m["psi"], dtype=np.float64)
+    assert all(om.strides[f] + om.n_elements[f][0] * om.n_elements[f][1] <= psi.size for f in range(6))
+    om.n_psi = psi.size
+    om.psi = _dp(psi)
+    om._psi = psi
+    return om
+
+
 def ffat_get_map_val(m, p):
     p = np.ascontiguousarray(p, dtype=np.float64)
     return lib().or_ffat_get_map_val(C.byref(m), _dp(p))

@@ -86,12 +86,22 @@ def run_engine(objs, events, n_buffers, split=None, frames=B, rate=orc.SAMPLE_RA
         eng.close()
 
 
+def is_uniform_cube(m):
+    """True when every geometry field of the map dict is what synth.uniform_cube_geometry gives for its centre, cell size and
+    n_elements[0][0] -- the maps orc.uniform_cube rebuilds exactly"""
+    g = synth.uniform_cube_geometry(m["center"], m["cell_size"], int(m["n_elements"][0][0]))
+    return all(np.array_equal(np.asarray(m[key], dtype=np.float64), np.asarray(val, dtype=np.float64)) for key, val in g.items())
+
+
+def oracle_map(m):
+    """the oracle's map for one map dict: a uniform cube as before (or_ffat_make_uniform_cube), any other box field by field"""
+    if is_uniform_cube(m):
+        return orc.uniform_cube(m["mode_id"], m["k"], m["center"], m["cell_size"], int(m["n_elements"][0][0]), m["psi"])
+    return orc.ffat_map(m)
+
+
 def _oracle_maps(maps):
-    out = []
-    for m in maps:
-        dim = int(m["n_elements"][0][0])
-        out.append(orc.uniform_cube(m["mode_id"], m["k"], m["center"], m["cell_size"], dim, m["psi"]))
-    return out
+    return [oracle_map(m) for m in maps]
 
 
 def _oracle_one(oi, o, events, n_buffers, l=None):
