@@ -672,6 +672,60 @@ int pbso_master_reset(pbso_engine *e);
  * out[2] = steps processed, out[3] = sets accepted */
 int pbso_master_info(pbso_engine *e, int64_t out[4]);
 
+/* Resampler bus: the output rate -- a rational polyphase sample-rate converter on a device buffer [C][n] (what the mixers, the
+ * reverb and the master bus write), so that a scene computed at 44100 Hz leaves the device at 48000 or 96000 Hz.  A plain FIR per
+ * output sample: parallel, bit-reproducible and independent of how the samples are cut into steps.
+ * Parameters at enable: C channels, 1 .. 8; rate_out; T taps per output sample, 1 .. 256; the Kaiser beta, finite, 0 <= beta <= 20;
+ * cutoff, finite, 0 < cutoff <= 1 (a fraction of the lower of the two Nyquist frequencies).  rate_in is the engine's sample_rate.
+ * L = rate_out / gcd(rate_in, rate_out), M = rate_in / gcd(rate_in, rate_out); both must be <= 4096 and L * T <= 1 << 18, else
+ * PBSO_ERR_INVALID.
+ * Prototype: N = L * T taps, computed once on the host in fp64 at enable and rounded to f32 once.  With c = (N - 1) / 2, x = j - c
+ * and fc = cutoff * 0.5 / max(L, M),
+ *     g[j] = L * 2 fc * sinc(2 fc x) * I0(beta * sqrt(1 - (2 x / (N - 1))^2)) / I0(beta)
+ * sinc(a) = sin(pi a) / (pi a), 1 at a = 0; the window is 1 for N = 1; I0 is the power series sum of ((x / 2)^k / k!)^2, summed in
+ * ascending k until a term is below 1e-17 of the sum.  The phase table is h[phi][k] = (float)g[k * L + phi], [L][T];
+ * pbso_resample_taps reads it back.
+ * Clock: t counts input samples and m output samples, both 64-bit and from the enable (or the last reset); u_c(t) is input channel
+ * c, 0 for t < 0.  Output m reads at i = floor(m * M / L) with phase phi = (m * M) mod L.  A call that processes the input samples
+ * [t, t + n) produces exactly the outputs m with t <= i < t + n: m from ceil(t * L / M) to ceil((t + n) * L / M) - 1.  Their number
+ * differs from call to call and is at most ceil(n * L / M) (pbso_resample_max_out): for 160 / 147 and n = 513 it is 559, then 558.
+ * Order of arithmetic:
+ *     acc = 0.f; for k = T-1 down to 0: acc = fmaf(h[phi][k], u_c(i - k), acc);   y_c(m) = acc
+ * one f32 fmaf chain, nothing split over accumulators.  Subnormals are kept.  The output is the input delayed by (N - 1) / (2 L)
+ * input samples, which is (N - 1) / (2 M) output samples.
+ * State: the device keeps the last T - 1 input samples of every channel, double-buffered as the master bus's history.  Between
+ * calls the host keeps only p0 = m_lo * M - t * L, which lies in [0, M), and counters: output j of a call has position p0 + j * M,
+ * so that i - t = position div L and phi = position mod L.  The device never multiplies an absolute index; the output depends only
+ * on the input samples, not on how they were cut into steps.
+ * pbso_resample processes n = the last step's n_buffers * frames_per_buffer samples: d_in [C][n] f32 on the device, required; d_out
+ * [C][out_stride] f32 with out_stride >= ceil(n * L / M), must not overlap d_in, or NULL for an engine-owned buffer whose stride is
+ * n_out (out_stride is not read then).  *n_out (may be NULL) receives the number of outputs per channel; the words of a row behind
+ * them are not written.  Asynchronous on the engine's stream.  While enabled, every step is processed exactly once: a second call
+ * for the same step, a call after a step that was skipped or a call before any step is PBSO_ERR_STATE.  A step delivered to host
+ * memory is not an error here: the input is the caller's buffer.  A refused call changes nothing.  The reset makes the history
+ * silent, sets t = m = p0 = 0 and arms the stage for the next step.  The stage knows nothing of the other buses.  A device group
+ * has none.
+ * Meters of the last call: one record per channel.  Resampling reconstructs the signal between the input samples, where it can be
+ * larger than at any of them: behind a limiter the output can overshoot the limiter's ceiling (by a few tenths of a dB on dense
+ * material, by more on a clipped square).  out_peak and n_over make that visible; a caller that must not exceed full scale gives
+ * the master bus a ceiling with headroom (0.9 is a common choice) rather than 1.  The PCM conversion saturates.
+ * PCM: (int16_t)lrintf(fminf(fmaxf(y, -1.f), 1.f) * 32767.f), interleaved [n_out][C], converted on the device.                  */
+typedef struct pbso_resample_meter {
+    float out_peak;      /* max |y_c| over the call's outputs (0 when it had none) */
+    int32_t n_over;      /* count of |y_c| > 1.f */
+} pbso_resample_meter;   /* 8 bytes */
+int pbso_resample_enable(pbso_engine *e, int n_channels, int rate_out, int taps, double beta, double cutoff);   /* after finalize */
+int pbso_resample(pbso_engine *e, const void *d_in, void *d_out, int64_t out_stride, int64_t *n_out);
+int pbso_resample_max_out(pbso_engine *e, int n_buffers, int64_t *out);     /* ceil(n L / M), n = n_buffers * frames_per_buffer */
+int pbso_read_resample(pbso_engine *e, float *host_out, size_t n);          /* planar [C][n_out] of the last call, synchronous; n = C * n_out */
+int pbso_read_resample_pcm16(pbso_engine *e, int16_t *host_out, size_t n);  /* interleaved [n_out][C]; n as above */
+int pbso_read_resample_meters(pbso_engine *e, pbso_resample_meter *out, size_t n_channels);   /* [C] */
+int pbso_resample_taps(pbso_engine *e, float *out, size_t n);               /* the phase table [L][T]; n = L * T */
+int pbso_resample_reset(pbso_engine *e);
+/* out[0] = t, out[1] = m, out[2] = steps processed, out[3] = L, out[4] = M, out[5] = T, out[6] = N - 1 (the numerator of the delay:
+ * over 2 L in input samples, over 2 M in output samples), out[7] = n_out of the last call */
+int pbso_resample_info(pbso_engine *e, int64_t out[8]);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a

@@ -42,6 +42,9 @@ EXPORTS = [
     # the master bus (gain, look-ahead limiter, meters and 16-bit PCM on a bus [C][n])
     "pbso_master_enable", "pbso_master_set_gain", "pbso_master", "pbso_read_master", "pbso_read_master_pcm16",
     "pbso_read_master_meters", "pbso_master_window", "pbso_master_reset", "pbso_master_info",
+    # the resampler bus (a bus [C][n] at sample_rate out at another rate: rational polyphase, meters and 16-bit PCM)
+    "pbso_resample_enable", "pbso_resample", "pbso_resample_max_out", "pbso_read_resample", "pbso_read_resample_pcm16",
+    "pbso_read_resample_meters", "pbso_resample_taps", "pbso_resample_reset", "pbso_resample_info",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -112,6 +115,11 @@ class MasterMeter(C.Structure):
     """pbso_master_meter: one record per (buffer, channel) of a pbso_master call, 24 bytes"""
     _fields_ = [("in_peak", C.c_float), ("out_peak", C.c_float), ("min_gain", C.c_float), ("n_limited", C.c_int32),
                 ("sumsq", C.c_double)]
+
+
+class ResampleMeter(C.Structure):
+    """pbso_resample_meter: one record per channel of a pbso_resample call, 8 bytes"""
+    _fields_ = [("out_peak", C.c_float), ("n_over", C.c_int32)]
 
 
 class EngineInfo(C.Structure):
@@ -249,6 +257,16 @@ def lib():
         l.pbso_master_window.argtypes = [vp, fp, C.c_size_t]
         l.pbso_master_reset.argtypes = [vp]
         l.pbso_master_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_resample"):
+        l.pbso_resample_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+        l.pbso_resample.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        l.pbso_resample_max_out.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
+        l.pbso_read_resample.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_read_resample_pcm16.argtypes = [vp, C.POINTER(C.c_int16), C.c_size_t]
+        l.pbso_read_resample_meters.argtypes = [vp, C.POINTER(ResampleMeter), C.c_size_t]
+        l.pbso_resample_taps.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_resample_reset.argtypes = [vp]
+        l.pbso_resample_info.argtypes = [vp, C.POINTER(C.c_int64)]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_set_material"):
         l.pbso_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
         l.pbso_get_material.argtypes = [vp, C.c_int, C.POINTER(Material)]

@@ -669,6 +669,75 @@ int pbso_master_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_resample_enable(pbso_engine *e, int n_channels, int rate_out, int taps, double beta, double cutoff) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->resample_enable(n_channels, rate_out, taps, beta, cutoff);
+    GUARD_END(e)
+}
+
+int pbso_resample(pbso_engine *e, const void *d_in, void *d_out, int64_t out_stride, int64_t *n_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->resample(d_in, d_out, out_stride, n_out);
+    GUARD_END(e)
+}
+
+int pbso_resample_max_out(pbso_engine *e, int n_buffers, int64_t *out) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->resample_max_out(n_buffers, out);
+    GUARD_END(e)
+}
+
+int pbso_read_resample(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_resample(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_read_resample_pcm16(pbso_engine *e, int16_t *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_resample_pcm16(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_read_resample_meters(pbso_engine *e, pbso_resample_meter *out, size_t n_channels) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_resample_meters(out, n_channels);
+    GUARD_END(e)
+}
+
+int pbso_resample_taps(pbso_engine *e, float *out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->resample_taps(out, n);
+    GUARD_END(e)
+}
+
+int pbso_resample_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->resample_reset();
+    GUARD_END(e)
+}
+
+int pbso_resample_info(pbso_engine *e, int64_t out[8]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->resample_info(out);
+    GUARD_END(e)
+}
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

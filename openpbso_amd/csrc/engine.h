@@ -29,6 +29,7 @@ struct SceneMix;         // scene_mix.cpp
 struct SceneFir;         // scene_fir.cpp
 struct SceneReverb;      // scene_reverb.cpp
 struct Master;           // master.cpp
+struct Resample;         // resample.cpp
 struct TrackPool;        // track_pool.cpp
 struct BusOut;           // bus_state.h
 struct BusWords;         // bus_clock.h
@@ -290,6 +291,16 @@ public:
     int master_window(float *out, size_t n);
     int master_reset();
     int master_info(int64_t out[4]);
+    // the resampler bus (resample.cpp, kernels_resample.hip): a caller's bus [C][n] at sample_rate out at another rate, L / M polyphase
+    int resample_enable(int n_channels, int rate_out, int taps, double beta, double cutoff);
+    int resample(const void *d_in, void *d_out, int64_t out_stride, int64_t *n_out);
+    int resample_max_out(int n_buffers, int64_t *out);
+    int read_resample(float *out, size_t n);
+    int read_resample_pcm16(int16_t *out, size_t n);
+    int read_resample_meters(pbso_resample_meter *out, size_t n_channels);
+    int resample_taps(float *out, size_t n);
+    int resample_reset();
+    int resample_info(int64_t out[8]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -562,6 +573,8 @@ private:
     void scene_reverb_release();
     Master *master_ = nullptr;                           // pbso_master_enable
     void master_release();
+    Resample *resample_ = nullptr;                       // pbso_resample_enable
+    void resample_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

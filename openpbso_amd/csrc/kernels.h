@@ -411,6 +411,15 @@ int launch_master(const float *in, int C, long long n, int B, const float *hist,
 // pcm [n][C] = (int16_t)lrintf(y[c][s] * 32767.f) of y [C][n]
 int launch_master_pcm16(const float *y, int C, long long n, short *pcm, hipStream_t stream);
 
+// pbso_resample (kernels_resample.hip): the resampler bus on [C][n].  Output j < n_out of channel c, at position p0 + j M (in units
+// of 1 / L input samples from in[c][0]; 0 <= p0 < M, and the last position div L < n), is one fmaf chain over the T taps of row
+// (position mod L) of h [L][T] and T samples of hist ++ in; hist [C][T - 1].  out [C][out_stride] (must not overlap in), meters [C]
+// of pbso_resample_meter (zeroed, then merged per workgroup); then hist_next = the last T - 1 samples of hist ++ in.
+int launch_resample(const float *in, int C, long long n, const float *hist, float *hist_next, const float *h, int L, int M, int T,
+                    long long p0, long long n_out, float *out, long long out_stride, void *meters, hipStream_t stream);
+// pcm [n][C] = (int16_t)lrintf(clamp(y[c][s], -1.f, 1.f) * 32767.f) of y [C][stride]
+int launch_resample_pcm16(const float *y, int C, long long n, long long stride, short *pcm, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -755,6 +755,62 @@ class Engine:
         self._chk(self._l.pbso_master_info(self._h, v))
         return {"t": v[0], "ramp_end": v[1], "calls": v[2], "sets": v[3]}
 
+    # -- resampler bus: a device buffer [C][n] at the engine's rate out at another rate, history kept across steps ----------------
+    def resample_enable(self, rate_out, n_channels, taps=32, beta=9.0, cutoff=0.9):
+        """pbso_resample_enable: from the next step on, every step is processed exactly once (resample)"""
+        self._chk(self._l.pbso_resample_enable(self._h, n_channels, rate_out, taps, beta, cutoff))
+        self._rs_channels, self._rs_n_out = n_channels, 0
+
+    def resample(self, d_in, d_out=None, out_stride=0):
+        """pbso_resample: the device buffer d_in [C][n_buffers * frames] f32 of the last step at the output rate into d_out
+        [C][out_stride] (None: the engine's own, stride n_out; must not overlap d_in).  Device pointers as integers.  Returns n_out,
+        the number of output samples per channel, which differs from call to call."""
+        vp = lambda p: None if p is None else C.c_void_p(p)
+        n_out = C.c_int64(0)
+        self._chk(self._l.pbso_resample(self._h, vp(d_in), vp(d_out), out_stride, C.byref(n_out)))
+        self._rs_n_out = n_out.value
+        return n_out.value
+
+    def resample_max_out(self, n_buffers):
+        """ceil(n L / M): the most outputs per channel a step of n_buffers can have"""
+        v = C.c_int64(0)
+        self._chk(self._l.pbso_resample_max_out(self._h, n_buffers, C.byref(v)))
+        return v.value
+
+    def read_resample(self):
+        """the last resampler output: [C][n_out] float32 (synchronous)"""
+        out = np.empty((self._rs_channels, self._rs_n_out), dtype=np.float32)
+        self._chk(self._l.pbso_read_resample(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def read_resample_pcm16(self):
+        """the last resampler output as interleaved 16-bit PCM, saturated and converted on the device: [n_out][C] int16"""
+        out = np.empty((self._rs_n_out, self._rs_channels), dtype=np.int16)
+        self._chk(self._l.pbso_read_resample_pcm16(self._h, out.ctypes.data_as(C.POINTER(C.c_int16)), out.size))
+        return out
+
+    def read_resample_meters(self):
+        """the last call's meters: a structured array [C] (out_peak, n_over)"""
+        out = np.empty(self._rs_channels, dtype=np.dtype(capi.ResampleMeter))
+        self._chk(self._l.pbso_read_resample_meters(self._h, out.ctypes.data_as(C.POINTER(capi.ResampleMeter)), out.size))
+        return out
+
+    def resample_taps(self):
+        """the phase table in force: [L][T] float32"""
+        i = self.resample_info()
+        out = np.empty((i["L"], i["T"]), dtype=np.float32)
+        self._chk(self._l.pbso_resample_taps(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def resample_reset(self):
+        self._chk(self._l.pbso_resample_reset(self._h))
+
+    def resample_info(self):
+        """pbso_resample_info: t, m, calls, L, M, T, N - 1 (the delay is that over 2 L input samples), n_out of the last call"""
+        v = (C.c_int64 * 8)()
+        self._chk(self._l.pbso_resample_info(self._h, v))
+        return {"t": v[0], "m": v[1], "calls": v[2], "L": v[3], "M": v[4], "T": v[5], "delay_num": v[6], "n_out": v[7]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

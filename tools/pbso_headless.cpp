@@ -53,6 +53,14 @@
 //                    the file has the length and alignment of the run without --limit.  --pcm16 writes a 16-bit PCM WAV (format 1)
 //                    converted on the device (pbso_read_master_pcm16); only with --limit.  One engine only: not with --devices;
 //                    not with --raw (the unscaled mix).
+//   --out-rate R [--rs-taps T] [--rs-beta B] [--rs-cutoff F]   the resampler bus (pbso_resample) behind whatever the tool would have
+//                    written -- the mono object mix, --pan, --fir, dry + wet with --reverb, and --limit's output when that is given:
+//                    the WAV's samples at R Hz instead of 44100, through T taps per output sample (default 32, 1 .. 256) of a
+//                    Kaiser-windowed sinc (beta B, default 9; cutoff F, default 0.9).  The WAV header carries R.  The converter
+//                    delays by (L T - 1) / (2 L) input samples (L = R / gcd(R, 44100)): with d = that plus --limit's look-ahead,
+//                    the tool steps enough more buffers with no hits to flush d, drops the first floor(d L / M + 0.5) output
+//                    frames and writes ceil(buffers * 513 * L / M) of them.  --pcm16 beside it takes the resampler's saturating
+//                    PCM (pbso_read_resample_pcm16) and still needs --limit.  One engine only: not with --devices; not with --raw.
 //   --retune FILE    materials changed during the run (pbso_set_material; with --devices pbso_group_set_material): lines
 //                    <buffer> <copy> <material file> [keep|zero] give copy the file's material (the format of -t) from that
 //                    buffer on; keep (the default): the state carries on under the new coefficients, zero: it is cleared.  Every
@@ -72,6 +80,7 @@
 #include <vector>
 
 #include "openpbso_amd.h"
+#include "resample_clock.h"                              // (openpbso_amd/csrc: the resampler's limits and counts, no HIP in it)
 
 static void die(const std::string &msg) {
     std::fprintf(stderr, "pbso_headless: %s\n", msg.c_str());
@@ -481,6 +490,9 @@ int main(int argc, char **argv) {
     bool limit = false, pcm16 = false, master_flag = false;  // --limit; master_flag: one of its companions was given
     float limit_T = 1.f, master_gain = 1.f;
     int lookahead = 64, hold = 0;
+    int out_rate = 0, rs_taps = 32;                      // --out-rate; rs_flag: one of its companions was given
+    double rs_beta = 9.0, rs_cutoff = 0.9;
+    bool rs_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + a); return argv[++i]; };
@@ -522,6 +534,10 @@ int main(int argc, char **argv) {
         else if (a == "--hold") { master_flag = true; hold = std::atoi(val().c_str()); }
         else if (a == "--gain") { master_flag = true; master_gain = (float)std::atof(val().c_str()); }
         else if (a == "--pcm16") pcm16 = true;
+        else if (a == "--out-rate") { out_rate = std::atoi(val().c_str()); if (out_rate < 1) die("--out-rate: the rates must be positive"); }
+        else if (a == "--rs-taps") { rs_flag = true; rs_taps = std::atoi(val().c_str()); }
+        else if (a == "--rs-beta") { rs_flag = true; rs_beta = std::atof(val().c_str()); }
+        else if (a == "--rs-cutoff") { rs_flag = true; rs_cutoff = std::atof(val().c_str()); }
         else die("unknown flag " + a);
     }
     if (pcm16 && !limit) die("--pcm16 needs --limit T: an integer WAV clips without a ceiling");
@@ -533,6 +549,15 @@ int main(int argc, char **argv) {
         if (lookahead < 1 || lookahead > 4096) die("--lookahead must be 1 .. 4096");
         if (hold < 0 || hold > 65536) die("--hold must be 0 .. 65536");
         if (!std::isfinite(master_gain)) die("--gain must be finite");
+    }
+    if (rs_flag && !out_rate) die("--rs-taps, --rs-beta and --rs-cutoff belong to --out-rate R");
+    int rs_L = 1, rs_M = 1;
+    if (out_rate) {
+        if (!devices_arg.empty()) die("--out-rate runs on one engine, not through a device group (--devices)");
+        if (!raw.empty()) die("--raw dumps the unscaled mix at 44100 Hz: not with --out-rate");
+        if (const char *why = pbso::resample_refusal(PBSO_SAMPLE_RATE, out_rate, rs_taps, rs_beta, rs_cutoff))
+            die(std::string("--out-rate from 44100 (L = R / gcd, M = 44100 / gcd): ") + why);
+        pbso::resample_reduce(PBSO_SAMPLE_RATE, out_rate, rs_L, rs_M);
     }
     if (!d.empty()) {                                   // fixed directory structure, tools/...:480-495
         if (name.empty()) name = guess_name(d);
@@ -807,7 +832,13 @@ int main(int argc, char **argv) {
         std::memcpy(scene.reverb.data(), bytes.data(), bytes.size());
     }
     std::vector<float> sound((size_t)n_buffers * PBSO_FRAMES_PER_BUFFER);
-    std::vector<int16_t> pcm;                            // --pcm16: the master bus's frames, interleaved, segment behind segment
+    std::vector<int16_t> pcm;                            // --pcm16: the master bus's (the resampler's) frames, interleaved, segment behind segment
+    std::vector<std::vector<float>> resampled;           // --out-rate: the resampler's output per channel, segment behind segment
+    // --out-rate: the delay in front of the file is d = look-ahead + (L T - 1) / (2 L) input samples = rs_delay_num / (2 L); the
+    // output frames dropped for it, floor(d L / M + 0.5), and the frames written, ceil(buffers * 513 * L / M)
+    const long long rs_delay_num = out_rate ? 2LL * rs_L * (limit ? lookahead : 0) + ((long long)rs_L * rs_taps - 1) : 0;
+    const long long rs_drop = out_rate ? (rs_delay_num + rs_M) / (2LL * rs_M) : 0;
+    const long long rs_keep = out_rate ? pbso::resample_max_out((long long)n_buffers * PBSO_FRAMES_PER_BUFFER, rs_L, rs_M) : 0;
     double device_ms = 0;
     if (!devices.empty()) {
         run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, retune, sound);
@@ -828,7 +859,7 @@ int main(int argc, char **argv) {
         if (path.empty()) check(e, pbso_set_use_transfer(e, obj, 0, 0), "set_use_transfer");   // unit transfer
         const std::vector<int> track_ids = create_tracks(e, tracks);
         for (const Hit &h : hit_list) {
-            if (limit && h.b >= n_buffers) continue;         // (the tail behind the run: no hits, as the run without --limit has none)
+            if ((limit || out_rate) && h.b >= n_buffers) continue;   // (the tail behind the run: no hits, as the run without --limit has none)
             rc = enqueue_hit(e, obj, h, track_ids, h.b);
             check(e, rc, h.track < 0 ? "enqueue_force" : "enqueue_track_force");
             if (rc == 0) die("force queue full");
@@ -840,17 +871,44 @@ int main(int argc, char **argv) {
         // --limit: n_tail more buffers behind the scripts; every segment read back goes, scaled as the WAV would have been, through
         // the master bus, and what comes out replaces it in `sound` (PCM: in `pcm`, interleaved)
         const int channels_out = mixed ? scene.channels : 1;
-        const int n_tail = limit ? (lookahead + PBSO_FRAMES_PER_BUFFER - 1) / PBSO_FRAMES_PER_BUFFER : 0, n_run = n_buffers + n_tail;
+        int n_tail = limit ? (lookahead + PBSO_FRAMES_PER_BUFFER - 1) / PBSO_FRAMES_PER_BUFFER : 0;
+        if (out_rate) {
+            // --out-rate: as many as hold d, and then as many as it takes until the outputs dropped and written are all there
+            n_tail = (int)((rs_delay_num + 2LL * rs_L * PBSO_FRAMES_PER_BUFFER - 1) / (2LL * rs_L * PBSO_FRAMES_PER_BUFFER));
+            while (pbso::resample_max_out((long long)(n_buffers + n_tail) * PBSO_FRAMES_PER_BUFFER, rs_L, rs_M) < rs_drop + rs_keep) ++n_tail;
+        }
+        const int n_run = n_buffers + n_tail;
+        const bool post = limit || out_rate;                 // the segments go through a bus behind the mix
         void *m_in = nullptr;
+        if (post && pbso_host_alloc((size_t)channels_out * n_run * PBSO_FRAMES_PER_BUFFER * sizeof(float), &m_in) != PBSO_OK)
+            die("cannot allocate the master bus's input");
         if (limit) {
-            if (pbso_host_alloc((size_t)channels_out * n_run * PBSO_FRAMES_PER_BUFFER * sizeof(float), &m_in) != PBSO_OK)
-                die("cannot allocate the master bus's input");
             check(e, pbso_master_enable(e, channels_out, limit_T, lookahead, hold, 0), "master_enable");
             check(e, pbso_master_set_gain(e, master_gain), "master_set_gain");
+        }
+        if (out_rate) {
+            check(e, pbso_resample_enable(e, channels_out, out_rate, rs_taps, rs_beta, rs_cutoff), "resample_enable");
+            resampled.resize(channels_out);
         }
         auto master_segment = [&](std::vector<float> &seg) {         // seg [C][row], the last step's
             float *in = (float *)m_in;
             for (size_t i = 0; i < seg.size(); ++i) in[i] = (float)((double)seg[i] / 1E10);
+            if (out_rate) {
+                // the limiter in place (its input is read before anything is written), the resampler behind it from the same buffer
+                if (limit) check(e, pbso_master(e, m_in, m_in), "master");
+                int64_t k = 0;
+                check(e, pbso_resample(e, m_in, nullptr, 0, &k), "resample");
+                if (pcm16) {
+                    const size_t at = pcm.size();
+                    pcm.resize(at + (size_t)k * channels_out);
+                    check(e, pbso_read_resample_pcm16(e, pcm.data() + at, (size_t)k * channels_out), "read_resample_pcm16");
+                } else {
+                    std::vector<float> y((size_t)k * channels_out);
+                    check(e, pbso_read_resample(e, y.data(), y.size()), "read_resample");
+                    for (int c = 0; c < channels_out; ++c) resampled[c].insert(resampled[c].end(), y.begin() + (size_t)c * k, y.begin() + (size_t)(c + 1) * k);
+                }
+                return;
+            }
             check(e, pbso_master(e, m_in, nullptr), "master");
             if (pcm16) {
                 const size_t at = pcm.size();
@@ -911,7 +969,7 @@ int main(int argc, char **argv) {
                 } else {
                     check(e, pbso_read_scene_mix(e, seg.data(), seg.size()), "read_scene_mix");
                 }
-                if (limit) master_segment(seg);
+                if (post) master_segment(seg);
                 for (int c = 0; c < C; ++c)
                     std::copy(seg.begin() + (size_t)c * row, seg.begin() + (size_t)(c + 1) * row,
                               sound.begin() + (size_t)c * total + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
@@ -925,7 +983,7 @@ int main(int argc, char **argv) {
                 feed_strokes(e, strokes, stroke_ids, stroke_shift, 0, n_buffers, feed);
                 check(e, pbso_step(e, n_run), "step");
                 check(e, pbso_read_audio(e, sound.data(), sound.size()), "read_audio");
-                if (limit) master_segment(sound);
+                if (post) master_segment(sound);
             } else {
                 // the segments between the material script's change points (--limit's tail behind the last one)
                 std::vector<int> cuts = retune.cut({0, n_buffers}, n_buffers);
@@ -937,12 +995,12 @@ int main(int argc, char **argv) {
                     check(e, pbso_step(e, cuts[k + 1] - cuts[k]), "step");
                     seg.resize((size_t)(cuts[k + 1] - cuts[k]) * PBSO_FRAMES_PER_BUFFER);
                     check(e, pbso_read_audio(e, seg.data(), seg.size()), "read_audio");
-                    if (limit) master_segment(seg);
+                    if (post) master_segment(seg);
                     std::copy(seg.begin(), seg.end(), sound.begin() + (size_t)cuts[k] * PBSO_FRAMES_PER_BUFFER);
                 }
             }
         }
-        if (limit) check(e, pbso_sync(e), "sync");
+        if (post) check(e, pbso_sync(e), "sync");
         pbso_host_free(m_in);
         pbso_engine_info info;
         check(e, pbso_get_info(e, &info), "get_info");
@@ -951,6 +1009,23 @@ int main(int argc, char **argv) {
     }
     // C channels interleaved (mono: as it stands)
     const int channels = mixed ? scene.channels : 1;
+    if (out_rate) {
+        // the resampler's output is in the WAV's scale already; it is d L / M output frames late
+        const size_t drop = (size_t)rs_drop, keep = (size_t)rs_keep;
+        if (pcm16) {
+            if (pcm.size() < (drop + keep) * channels) die("the resampler delivered fewer frames than the file holds");
+            write_wav_pcm16(out, std::vector<int16_t>(pcm.begin() + drop * channels, pcm.begin() + (drop + keep) * channels), out_rate, channels);
+        } else {
+            if (resampled[0].size() < drop + keep) die("the resampler delivered fewer frames than the file holds");
+            std::vector<float> wav(keep * channels);
+            for (size_t i = 0; i < keep; ++i)
+                for (int c = 0; c < channels; ++c) wav[i * channels + c] = resampled[c][drop + i];
+            write_wav_f32(out, wav, out_rate, channels);
+        }
+        std::printf("%d buffers (%.3f s of audio) in %.3f ms on the device, %d Hz -> %s\n", n_buffers,
+                    n_buffers * (double)PBSO_FRAMES_PER_BUFFER / PBSO_SAMPLE_RATE, device_ms, out_rate, out.c_str());
+        return 0;
+    }
     if (limit) {
         // the master bus's output is in the WAV's scale already; it is L samples late: frames L .. L + n_buffers * 513 are the file
         const size_t run = sound.size() / channels, keep = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
