@@ -517,6 +517,39 @@ int pbso_scene_mix_set(pbso_engine *e, const float *gain, const float *delay);  
 int pbso_scene_mix(pbso_engine *e, void *d_out);           /* the last step, async on the engine's stream: d_out [C][n_buffers * B] f32, or NULL = engine-owned */
 int pbso_read_scene_mix(pbso_engine *e, float *host_out, size_t n);   /* the last mix, synchronously; n = C * n_buffers * B */
 int pbso_scene_mix_reset(pbso_engine *e);
+/* The scene mix's SCHEDULE: sets that take effect at absolute samples the caller gives, any number of them inside one step, so
+ * that a source that moves along a path does not cut the run at every change point.
+ * EFFECT.  A scheduled set does to every parameter exactly what pbso_scene_mix_set does, with t_set given by the caller instead
+ *   of "the first sample of the next mixed step": p_from = the value at t_set - 1 of the record in force at t_set - 1 (a set
+ *   during a running ramp starts from the current value), slope = (p_to - p_from) / R divided once, R the ramp_samples of the
+ *   enable.  The first set after enable / reset takes effect without a ramp, whichever call made it.  delay == NULL leaves the
+ *   delay records untouched.  At sample t the record in force is that of the latest set with t_set <= t, and the per-sample
+ *   arithmetic above is applied to it, word for word: the output still depends on the rows, the values set and the absolute
+ *   samples at which they took effect only, not on how the samples are cut into steps -- a schedule mixed in one step equals, bit
+ *   for bit, the same rows cut at every t_set with pbso_scene_mix_set before each piece.
+ * VALIDATION, ALL OR NOTHING.  t_set must be >= the next mixed sample (out[0] of pbso_scene_mix_info) and strictly greater than
+ *   the last pending scheduled set's, and the values are validated as pbso_scene_mix_set validates them; otherwise
+ *   PBSO_ERR_INVALID.  pbso_scene_mix_schedule validates all of its sets before it takes any: a refused call changes nothing.
+ *   PBSO_ERR_STATE before the enable.  n_sets == 0 is accepted.
+ * LIFETIME.  A set scheduled beyond the next step stays pending until the step that contains it.  At most 65 536 sets may take
+ *   effect inside one mixed step: with more, pbso_scene_mix returns PBSO_ERR_INVALID and nothing has changed (step in shorter
+ *   pieces, or clear the schedule).  If the device memory for a step's records (n_sets_in_step + 1 blocks of C * n_objects * 64
+ *   bytes) cannot be allocated, pbso_scene_mix returns PBSO_ERR_NOMEM and nothing has changed.
+ * WITH pbso_scene_mix_set.  While scheduled sets are pending pbso_scene_mix_set returns PBSO_ERR_STATE; with none pending it
+ *   behaves exactly as without a schedule.  After a drained schedule it continues from the value the schedule left, mid-ramp
+ *   included: as if every scheduled set had been a plain set between two steps cut at its sample.  (It then waits for the mix
+ *   that took the last scheduled sets, not for more.)
+ * pbso_scene_mix_clear_schedule drops the sets not yet in force.  pbso_scene_mix_reset and a new pbso_scene_mix_enable drop them
+ *   too; the reset keeps the targets last IN FORCE.
+ * pbso_scene_mix_info: out[0] = t of the next mixed sample, out[1] = scheduled sets still pending (t_set >= out[0]), out[2] = mixes
+ *   done, out[3] = sets accepted (plain and scheduled, each set of a pbso_scene_mix_schedule call counted); out[2] and out[3]
+ *   count from the enable.                                                                                                      */
+int pbso_scene_mix_set_at(pbso_engine *e, int64_t t_set, const float *gain, const float *delay);   /* one scheduled set; [C][n_objects] each */
+int pbso_scene_mix_schedule(pbso_engine *e, int n_sets, const int64_t *t_set,
+                            const float *gain  /* [n_sets][C][n_objects] */,
+                            const float *delay /* [n_sets][C][n_objects], or NULL = unchanged by all of them */);
+int pbso_scene_mix_clear_schedule(pbso_engine *e);      /* drops the sets not yet in force */
+int pbso_scene_mix_info(pbso_engine *e, int64_t out[4]);
 
 /* Scene filter mix: a second, independent mixer beside the scene mix -- a K-tap FIR per (channel, object) instead of one gain and
  * delay: a head-related impulse response per ear, an air-absorption filter, a handful of early reflections.
@@ -802,6 +835,12 @@ int pbso_group_sync(pbso_group *g);
  * its own objects).  After pbso_group_finalize; the arguments as for a single engine.                                       */
 int pbso_group_scene_mix_enable(pbso_group *g, int n_channels, int max_delay, int ramp_samples);
 int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *delay);
+/* ... and its schedule on every local rank: gain / delay [n_sets][C][n_objects of the whole job] by global id, each rank taking
+ * its slice of every set.  The values are checked for the whole job before any rank takes a set; the times are checked by the
+ * ranks' engines, which are mixed in lockstep and hold one clock (pbso_scene_mix_info of any pbso_group_engine has the counts). */
+int pbso_group_scene_mix_set_at(pbso_group *g, int64_t t_set, const float *gain, const float *delay);
+int pbso_group_scene_mix_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *gain, const float *delay);
+int pbso_group_scene_mix_clear_schedule(pbso_group *g);
 /* the scene filter mix on every local rank; taps [C][n_objects of the whole job][K] and onset [n_objects of the whole job] by
  * global id.  After pbso_group_finalize; the arguments as for a single engine.                                              */
 int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int max_onset, int xfade_samples);

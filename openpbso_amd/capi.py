@@ -30,6 +30,9 @@ EXPORTS = [
     "pbso_step_to_host", "pbso_host_wait", "pbso_host_alloc", "pbso_host_free",
     # the scene mix (C channels, a ramped gain and fractional delay per channel and object)
     "pbso_scene_mix_enable", "pbso_scene_mix_set", "pbso_scene_mix", "pbso_read_scene_mix", "pbso_scene_mix_reset",
+    # ... and its schedule (sets that take effect at absolute samples, any number of them inside one step)
+    "pbso_scene_mix_set_at", "pbso_scene_mix_schedule", "pbso_scene_mix_clear_schedule", "pbso_scene_mix_info",
+    "pbso_group_scene_mix_set_at", "pbso_group_scene_mix_schedule", "pbso_group_scene_mix_clear_schedule",
     # the scene filter mix (C channels, K taps per channel and object behind an onset per object)
     "pbso_scene_fir_enable", "pbso_scene_fir_set", "pbso_scene_fir", "pbso_read_scene_fir", "pbso_scene_fir_reset", "pbso_scene_fir_info",
     "pbso_group_scene_fir_enable", "pbso_group_scene_fir_set",
@@ -224,6 +227,14 @@ def lib():
     l.pbso_scene_mix_reset.argtypes = [vp]
     l.pbso_group_scene_mix_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     l.pbso_group_scene_mix_set.argtypes = [vp, fp, fp]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_mix_schedule"):
+        l.pbso_scene_mix_set_at.argtypes = [vp, C.c_int64, fp, fp]
+        l.pbso_scene_mix_schedule.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), fp, fp]
+        l.pbso_scene_mix_clear_schedule.argtypes = [vp]
+        l.pbso_scene_mix_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_group_scene_mix_set_at.argtypes = [vp, C.c_int64, fp, fp]
+        l.pbso_group_scene_mix_schedule.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), fp, fp]
+        l.pbso_group_scene_mix_clear_schedule.argtypes = [vp]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_fir"):
         # (as the tracks above: an older build picked with PBSO_LIB has no filter mix)
         l.pbso_scene_fir_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -15,10 +15,7 @@ namespace pbso {
 // a set takes effect at sample t, the first of the next step; a running ramp is left at the value it had one sample before
 // (from_current false: the first set after enable / reset, which takes effect without a ramp)
 inline void ramp_set(SceneParam &q, double v, long long t, int R, bool from_current) {
-    q.from = from_current ? ramp_value(q, t - 1, R) : v;
-    q.to = v;
-    q.t_set = t;
-    q.slope = R ? (q.to - q.from) / (double)R : 0.0;
+    q = ramp_next(q, v, true, t, R, from_current);
 }
 // reset: the parameter stays at its target, its ramp finished
 inline void ramp_settle(SceneParam &q) {

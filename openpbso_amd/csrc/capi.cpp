@@ -462,6 +462,34 @@ int pbso_scene_mix_set(pbso_engine *e, const float *gain, const float *delay) {
     GUARD_END(e)
 }
 
+int pbso_scene_mix_set_at(pbso_engine *e, int64_t t_set, const float *gain, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_mix_schedule("scene_mix_set_at", 1, &t_set, gain, delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_mix_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const float *gain, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_mix_schedule("scene_mix_schedule", n_sets, t_set, gain, delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_mix_clear_schedule(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_mix_clear_schedule();
+    GUARD_END(e)
+}
+
+int pbso_scene_mix_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_mix_info(out);
+    GUARD_END(e)
+}
+
 int pbso_scene_mix(pbso_engine *e, void *d_out) {
     NEED(e);
     GUARD_BEGIN

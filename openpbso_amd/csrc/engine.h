@@ -263,6 +263,10 @@ public:
     int scene_mix(void *d_out);
     int read_scene_mix(float *out, size_t n);
     int scene_mix_reset();
+    // ... and its schedule: sets that take effect at absolute samples given by the caller (`call`: the entry point, for the messages)
+    int scene_mix_schedule(const char *call, int n_sets, const int64_t *t_set, const float *gain, const float *delay);
+    int scene_mix_clear_schedule();
+    int scene_mix_info(int64_t out[4]);
     // the scene filter mix (scene_fir.cpp, kernels_fir.hip): C channels, K taps per (channel, object) behind an onset per object
     int scene_fir_enable(int n_channels, int n_taps, int max_onset, int xfade_samples);
     int scene_fir_set(const float *taps, const int *onset);

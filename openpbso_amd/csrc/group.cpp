@@ -558,6 +558,58 @@ int pbso_group_scene_mix_set(pbso_group *g, const float *gain, const float *dela
     return PBSO_OK;
 }
 
+// the scene mix's schedule: every rank takes the slice of its own objects of every set, [n_sets][C][n_local].  The values are
+// checked for the whole job first; the times are checked by the engines, which are mixed in lockstep and so hold one clock and one
+// pending list: the first rank's refusal is every rank's, and no rank has taken anything by then.
+static int group_scene_mix_schedule(pbso_group *g, const char *call, int n_sets, const int64_t *t_set, const float *gain, const float *delay) {
+    const std::string name(call);
+    if (!g || !g->scene_on) return gfail(g, PBSO_ERR_STATE, name + ": the group's scene mixer is not enabled");
+    if (n_sets < 0) return gfail(g, PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return gfail(g, PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!gain) return gfail(g, PBSO_ERR_INVALID, name + ": gain is NULL");
+    const size_t n = (size_t)g->n_objects, cn = (size_t)g->scene_c * n;
+    for (size_t i = 0; i < (size_t)n_sets * cn; ++i) {
+        if (!std::isfinite(gain[i])) return gfail(g, PBSO_ERR_INVALID, name + ": a gain is not finite");
+        if (delay && !(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)g->scene_max_delay))
+            return gfail(g, PBSO_ERR_INVALID, name + ": a delay is not finite or outside [0, max_delay]");
+    }
+    try {
+        std::vector<float> gs, ds;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local, cl = (size_t)g->scene_c * nl;
+            gs.resize((size_t)n_sets * cl);
+            ds.resize(delay ? gs.size() : 0);
+            for (size_t k = 0; k < (size_t)n_sets; ++k)
+                for (size_t c = 0; c < (size_t)g->scene_c; ++c)
+                    for (size_t l = 0; l < nl; ++l) {
+                        gs[k * cl + c * nl + l] = gain[k * cn + c * n + lo + l];
+                        if (delay) ds[k * cl + c * nl + l] = delay[k * cn + c * n + lo + l];
+                    }
+            GENG(g, rk, pbso_scene_mix_schedule(rk.eng, n_sets, t_set, gs.data(), delay ? ds.data() : nullptr));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
+    return PBSO_OK;
+}
+
+int pbso_group_scene_mix_set_at(pbso_group *g, int64_t t_set, const float *gain, const float *delay) {
+    return group_scene_mix_schedule(g, "scene_mix_set_at", 1, &t_set, gain, delay);
+}
+
+int pbso_group_scene_mix_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *gain, const float *delay) {
+    return group_scene_mix_schedule(g, "scene_mix_schedule", n_sets, t_set, gain, delay);
+}
+
+int pbso_group_scene_mix_clear_schedule(pbso_group *g) {
+    if (!g || !g->scene_on) return gfail(g, PBSO_ERR_STATE, "scene_mix_clear_schedule: the group's scene mixer is not enabled");
+    for (Rank &rk : g->ranks)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_mix_clear_schedule(rk.eng));
+    return PBSO_OK;
+}
+
 int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int max_onset, int xfade_samples) {
     if (!g || !g->finalized) return gfail(g, PBSO_ERR_STATE, "scene_fir_enable before finalize");
     if (n_channels < 1 || n_channels > pbso::SCENE_MAX_CHANNELS || n_taps < 1 || n_taps > pbso::SCENE_FIR_MAX_TAPS || max_onset < 0 ||

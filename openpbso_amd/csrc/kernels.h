@@ -359,6 +359,15 @@ constexpr int SCENE_MAX_CHANNELS = 8;
 // samples of hist ++ rows (a second kernel on the stream: the mix has read hist by then)
 int launch_scene_mix(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const SceneParam *params,
                      int C, int ramp, long long t0, float *parts, float *out, hipStream_t stream);
+// The same step with K >= 1 scheduled sets taking effect inside it (pbso_scene_mix_schedule), at the ascending absolute samples
+// t_set[K] in [t0, t0 + n): targets [K][2][C * n_obj] f32 (gains, then delays; the delays of set k are read only where
+// has_delay[k] != 0, else they stay as they are).  scene_schedule_expand_kernel chains ramp_next (scene_ramp.h) over the sets:
+// records [K + 1][C][n_obj][2], block 0 = params as they are, block k + 1 in force from t_set[k] on; params becomes the last
+// block.  Stage 1 then reads the block in force at each sample.  any_set 0: set 0 is the first after enable / reset (no ramp).
+constexpr int SCENE_MAX_SETS_PER_STEP = 65536;
+int launch_scene_mix_schedule(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, SceneParam *params,
+                              int C, int ramp, long long t0, float *parts, float *out, hipStream_t stream, SceneParam *records,
+                              const long long *t_set, const int *has_delay, const float *targets, int K, int any_set);
 
 // pbso_scene_fir (kernels_fir.hip): C output channels, K f32 taps per (channel, object) behind an integer onset per object, as
 // one fmaf chain per (channel, group of 32 objects, sample) on the f32 MFMA; the groups' rows then in group order.

@@ -7,8 +7,55 @@
 
 #include <cmath>
 #include <cstring>
+#include <deque>
 
 namespace pbso {
+
+// a scheduled set that is not in force yet: its targets in f32 as given, the gains [C][N], then the delays where it has any
+struct PendingSet { long long t; bool has_delay; std::vector<float> v; };
+
+// Pinned staging of one step's scheduled sets, in a ring as UploadRing, but each slot grows to what a step needs.  A slot is
+// rewritten (or freed for a larger one) only once the copy that last read it is done.
+struct StagingRing {
+    static constexpr int SLOTS = UploadRing::UP_SLOTS;
+    char *block[SLOTS] = {};
+    size_t cap[SLOTS] = {};
+    hipEvent_t ev[SLOTS] = {};
+    bool used[SLOTS] = {};
+    int slot = 0;
+    StagingRing() = default;
+    StagingRing(const StagingRing &) = delete;
+    StagingRing &operator=(const StagingRing &) = delete;
+    ~StagingRing() {
+        for (int i = 0; i < SLOTS; ++i) {
+            if (block[i]) (void)hipHostFree(block[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+    // the next slot's block, at least `bytes` long, once its last copy has left it
+    hipError_t acquire(size_t bytes, char *&b) {
+        hipError_t e = hipSuccess;
+        if (!ev[slot] && (e = hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming)) != hipSuccess) { ev[slot] = nullptr; return e; }
+        if (used[slot] && (e = hipEventSynchronize(ev[slot])) != hipSuccess) return e;
+        used[slot] = false;
+        if (cap[slot] < bytes) {
+            if (block[slot]) (void)hipHostFree(block[slot]);
+            block[slot] = nullptr;
+            cap[slot] = 0;
+            if ((e = hipHostMalloc((void **)&block[slot], bytes, hipHostMallocDefault)) != hipSuccess) { block[slot] = nullptr; return e; }
+            cap[slot] = bytes;
+        }
+        b = block[slot];
+        return hipSuccess;
+    }
+    hipError_t record(hipStream_t s) {
+        const hipError_t e = hipEventRecord(ev[slot], s);
+        if (e != hipSuccess) return e;
+        used[slot] = true;
+        slot = (slot + 1) % SLOTS;
+        return hipSuccess;
+    }
+};
 
 struct SceneMix {
     int C = 0, N = 0, max_delay = 0, ramp = 0, H = 0;   // H = max_delay + 1 samples of history per object
@@ -20,6 +67,33 @@ struct SceneMix {
     DevMem<float> parts;                                 // partial rows [C][groups][n]
     DevMem<SceneParam> d_p;                              // the parameters on the device
     UploadRing up;                                       // blocks of p.size() parameters
+    // the schedule (pbso_scene_mix_schedule): the sets not yet in force, ascending in t and none before clock.t; a mix takes those
+    // inside its step to the device, where they are expanded into the step's records (scene_schedule_expand_kernel) and the last
+    // one's block becomes d_p.  p then lags behind d_p (p_stale) until the copy back, queued behind the mix, is taken over.
+    std::deque<PendingSet> pending;
+    StagingRing stage;                                   // a step's times, has-delay flags and targets
+    DevMem<char> d_sets;                                 // ... on the device
+    DevMem<SceneParam> d_rec;                            // the step's records [K + 1][C][N][2]
+    SceneParam *p_back = nullptr;                        // pinned: d_p after the last mix that took scheduled sets
+    hipEvent_t ev_back = nullptr;
+    bool p_stale = false;
+    long long n_mixes = 0, n_sets = 0;                   // since the enable (pbso_scene_mix_info)
+    SceneMix() = default;
+    SceneMix(const SceneMix &) = delete;
+    SceneMix &operator=(const SceneMix &) = delete;
+    ~SceneMix() {
+        if (p_back) (void)hipHostFree(p_back);
+        if (ev_back) (void)hipEventDestroy(ev_back);
+    }
+    // p as the device has it, before anything reads or changes it: waits for the mix that took the scheduled sets, not for more
+    hipError_t refresh() {
+        if (!p_stale) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev_back);
+        if (e != hipSuccess) return e;
+        std::memcpy(p.data(), p_back, p.size() * sizeof(SceneParam));
+        p_stale = false;
+        return hipSuccess;
+    }
 };
 
 static const BusWords WORDS = {"scene_mix", "mixed", "the mixer", "audio", "mix", "n_channels"};
@@ -59,6 +133,14 @@ int Engine::scene_mix_enable(int C, int max_delay, int ramp) {
     case UploadRing::NO_EVENT: return hip_fail(hipErrorInvalidValue, "scene_mix_enable: hipEventCreate");
     case UploadRing::OK: break;
     }
+    if (hipHostMalloc((void **)&m->p_back, m->p.size() * sizeof(SceneParam), hipHostMallocDefault) != hipSuccess) {
+        m->p_back = nullptr;
+        return nomem("the parameters");
+    }
+    if (hipEventCreateWithFlags(&m->ev_back, hipEventDisableTiming) != hipSuccess) {
+        m->ev_back = nullptr;
+        return hip_fail(hipErrorInvalidValue, "scene_mix_enable: hipEventCreate");
+    }
     m->clock.arm(tot_steps_);
     scene_ = m.release();
     return PBSO_OK;
@@ -68,12 +150,14 @@ int Engine::scene_mix_set(const float *gain, const float *delay) {
     if (!scene_) return fail(PBSO_ERR_STATE, "scene_mix_set: the scene mixer is not enabled");
     if (!gain) return fail(PBSO_ERR_INVALID, "scene_mix_set: gain is NULL");
     SceneMix &m = *scene_;
+    if (!m.pending.empty()) return fail(PBSO_ERR_STATE, "scene_mix_set: scheduled sets are pending (pbso_scene_mix_clear_schedule drops them)");
     const size_t cn = (size_t)m.C * m.N;
     for (size_t i = 0; i < cn; ++i) {
         if (!std::isfinite(gain[i])) return fail(PBSO_ERR_INVALID, "scene_mix_set: a gain is not finite");
         if (delay && !(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)m.max_delay))
             return fail(PBSO_ERR_INVALID, "scene_mix_set: a delay is not finite or outside [0, max_delay]");
     }
+    HIPTRY(m.refresh());                                 // (after a drained schedule: from the value it left, mid-ramp included)
     // a set takes effect at the first sample of the next mixed step; during a ramp the new one starts from the current value
     for (size_t i = 0; i < cn; ++i) {
         ramp_set(m.p[2 * i], gain[i], m.clock.t, m.ramp, m.any_set);
@@ -81,6 +165,58 @@ int Engine::scene_mix_set(const float *gain, const float *delay) {
     }
     m.any_set = true;
     m.dirty = true;
+    ++m.n_sets;
+    return PBSO_OK;
+}
+
+// n_sets sets at the absolute samples t_set, gain / delay [n_sets][C][N] (delay NULL: unchanged by all of them); `call` names the
+// entry point in the messages.  All of them are checked before the first is taken.
+int Engine::scene_mix_schedule(const char *call, int n_sets, const int64_t *t_set, const float *gain, const float *delay) {
+    const std::string name(call);
+    if (!scene_) return fail(PBSO_ERR_STATE, name + ": the scene mixer is not enabled");
+    if (n_sets < 0) return fail(PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return fail(PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!gain) return fail(PBSO_ERR_INVALID, name + ": gain is NULL");
+    SceneMix &m = *scene_;
+    const size_t cn = (size_t)m.C * m.N;
+    long long after = m.pending.empty() ? m.clock.t - 1 : m.pending.back().t;       // every t_set lies behind this sample
+    for (int k = 0; k < n_sets; ++k) {
+        if ((long long)t_set[k] < m.clock.t) return fail(PBSO_ERR_INVALID, name + ": a t_set lies before the next mixed sample");
+        if ((long long)t_set[k] <= after) return fail(PBSO_ERR_INVALID, name + ": the t_set are not ascending behind the last pending set's");
+        after = (long long)t_set[k];
+    }
+    for (size_t i = 0; i < (size_t)n_sets * cn; ++i) {
+        if (!std::isfinite(gain[i])) return fail(PBSO_ERR_INVALID, name + ": a gain is not finite");
+        if (delay && !(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)m.max_delay))
+            return fail(PBSO_ERR_INVALID, name + ": a delay is not finite or outside [0, max_delay]");
+    }
+    std::deque<PendingSet> taken;                        // (built apart: a failed allocation leaves the pending list as it was)
+    for (int k = 0; k < n_sets; ++k) {
+        PendingSet q{(long long)t_set[k], delay != nullptr, {}};
+        q.v.assign(gain + (size_t)k * cn, gain + (size_t)(k + 1) * cn);
+        if (delay) q.v.insert(q.v.end(), delay + (size_t)k * cn, delay + (size_t)(k + 1) * cn);
+        taken.push_back(std::move(q));
+    }
+    for (PendingSet &q : taken) m.pending.push_back(std::move(q));
+    m.n_sets += n_sets;
+    return PBSO_OK;
+}
+
+int Engine::scene_mix_clear_schedule() {
+    if (!scene_) return fail(PBSO_ERR_STATE, "scene_mix_clear_schedule: the scene mixer is not enabled");
+    scene_->pending.clear();
+    return PBSO_OK;
+}
+
+int Engine::scene_mix_info(int64_t out[4]) {
+    if (!scene_) return fail(PBSO_ERR_STATE, "scene_mix_info: the scene mixer is not enabled");
+    if (!out) return fail(PBSO_ERR_INVALID, "scene_mix_info: out is NULL");
+    const SceneMix &m = *scene_;
+    out[0] = m.clock.t;
+    out[1] = (int64_t)m.pending.size();
+    out[2] = m.n_mixes;
+    out[3] = m.n_sets;
     return PBSO_OK;
 }
 
@@ -93,6 +229,20 @@ int Engine::scene_mix(void *d_out) {
     HIPTRY(hipSetDevice(desc_.device));
     const long long n = (long long)last_nb_ * B_;
     const int groups = mix_objects_groups(m.N);
+    // the scheduled sets that take effect inside this step (none lies before it); everything that can refuse comes before
+    // anything is taken or launched
+    size_t K = 0;
+    while (K < m.pending.size() && m.pending[K].t < m.clock.t + n) ++K;
+    if (K > (size_t)SCENE_MAX_SETS_PER_STEP)
+        return fail(PBSO_ERR_INVALID, "scene_mix: more than 65536 scheduled sets take effect inside this step (step in shorter pieces, or pbso_scene_mix_clear_schedule)");
+    const size_t cn = (size_t)m.C * m.N, off_flag = K * sizeof(long long), off_v = off_flag + K * sizeof(int),
+                 set_bytes = off_v + K * 2 * cn * sizeof(float);
+    char *h_sets = nullptr;
+    if (K) {
+        GROWTRY(grow(m.d_sets, set_bytes, stream_), "scene_mix: cannot allocate the step's scheduled sets", "scene_mix: scheduled sets");
+        GROWTRY(grow(m.d_rec, (K + 1) * m.p.size(), stream_), "scene_mix: cannot allocate the step's records", "scene_mix: records");
+        GROWTRY(m.stage.acquire(set_bytes, h_sets), "scene_mix: cannot allocate the staging of the step's scheduled sets", "scene_mix: staging");
+    }
     float *out;
     GROWTRY(m.out.resolve(d_out, (size_t)m.C * n, stream_, out), "scene_mix: cannot allocate the output", "scene_mix: output");
     GROWTRY(grow(m.parts, (size_t)m.C * groups * n, stream_), "scene_mix: cannot allocate the partial rows", "scene_mix: partial rows");
@@ -106,23 +256,50 @@ int Engine::scene_mix(void *d_out) {
         HIPTRY(m.up.record(stream_));
         m.dirty = false;
     }
-    const int lrc = launch_scene_mix(last_audio_, m.N, n, m.hist.cur(), m.hist.next(), m.H, m.d_p, m.C, m.ramp, m.clock.t, m.parts, out, stream_);
-    if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_scene_mix");
+    if (K == 0) {
+        const int lrc = launch_scene_mix(last_audio_, m.N, n, m.hist.cur(), m.hist.next(), m.H, m.d_p, m.C, m.ramp, m.clock.t, m.parts, out, stream_);
+        if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_scene_mix");
+    } else {
+        long long *h_t = (long long *)h_sets;
+        int *h_flag = (int *)(h_sets + off_flag);
+        float *h_v = (float *)(h_sets + off_v);
+        for (size_t k = 0; k < K; ++k) {
+            const PendingSet &q = m.pending[k];
+            h_t[k] = q.t;
+            h_flag[k] = q.has_delay ? 1 : 0;
+            std::memcpy(h_v + k * 2 * cn, q.v.data(), q.v.size() * sizeof(float));       // (no delays: that half is never read)
+        }
+        HIPTRY(hipMemcpyAsync(m.d_sets, h_sets, set_bytes, hipMemcpyHostToDevice, stream_));
+        HIPTRY(m.stage.record(stream_));
+        const int lrc = launch_scene_mix_schedule(last_audio_, m.N, n, m.hist.cur(), m.hist.next(), m.H, m.d_p, m.C, m.ramp, m.clock.t, m.parts,
+                                                  out, stream_, m.d_rec, (const long long *)m.d_sets.p, (const int *)(m.d_sets.p + off_flag),
+                                                  (const float *)(m.d_sets.p + off_v), (int)K, m.any_set ? 1 : 0);
+        if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_scene_mix_schedule");
+        // d_p is now the block of the last set; the host's copy follows behind the mix, and is taken over by who next needs it
+        HIPTRY(hipMemcpyAsync(m.p_back, m.d_p, m.p.size() * sizeof(SceneParam), hipMemcpyDeviceToHost, stream_));
+        HIPTRY(hipEventRecord(m.ev_back, stream_));
+        m.p_stale = true;
+        m.any_set = true;
+        m.pending.erase(m.pending.begin(), m.pending.begin() + (long)K);
+    }
     m.hist.flip();
     m.clock.advance(n, tot_steps_);
     m.out.wrote(out, last_nb_);
+    ++m.n_mixes;
     return PBSO_OK;
 }
 
 int Engine::read_scene_mix(float *out, size_t n) { return read_bus(scene_ ? &scene_->out : nullptr, scene_ ? scene_->C : 0, WORDS, out, n); }
 
-// the history back to silence, t back to 0; the gains and delays stay at their targets (ramps finished), and the next set takes
-// effect without a ramp.  Armed for the next step.
+// the history back to silence, t back to 0; the gains and delays stay at the targets last in force (ramps finished), the scheduled
+// sets still pending are dropped, and the next set takes effect without a ramp.  Armed for the next step.
 int Engine::scene_mix_reset() {
     if (!scene_) return fail(PBSO_ERR_STATE, "scene_mix_reset: the scene mixer is not enabled");
     SceneMix &m = *scene_;
     HIPTRY(hipSetDevice(desc_.device));
+    HIPTRY(m.refresh());
     HIPTRY(m.hist.reset(stream_));
+    m.pending.clear();
     for (SceneParam &q : m.p) ramp_settle(q);
     m.any_set = false;
     m.dirty = true;

@@ -155,6 +155,36 @@ class Group:
         assert g.size == self._scene_c * len(self._modes) and (d is None or d.size == g.size)
         self._chk(self._l.pbso_group_scene_mix_set(self._h, g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
 
+    def scene_mix_set_at(self, t_set, gain, delay=None):
+        """pbso_group_scene_mix_set_at: as scene_mix_set, taking effect at the absolute sample t_set"""
+        fp = C.POINTER(C.c_float)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        assert g.size == self._scene_c * len(self._modes) and (d is None or d.size == g.size)
+        self._chk(self._l.pbso_group_scene_mix_set_at(self._h, int(t_set), g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
+
+    def scene_mix_schedule(self, t_set, gain, delay=None):
+        """pbso_group_scene_mix_schedule: t_set [n_sets], gain / delay [n_sets][n_channels][n_objects of the job] by global id"""
+        fp = C.POINTER(C.c_float)
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        assert g.size == t.size * self._scene_c * len(self._modes) and (d is None or d.size == g.size)
+        self._chk(self._l.pbso_group_scene_mix_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)), g.ctypes.data_as(fp),
+                                                        None if d is None else d.ctypes.data_as(fp)))
+
+    def scene_mix_clear_schedule(self):
+        """pbso_group_scene_mix_clear_schedule: drops the scheduled sets not yet in force on every local rank"""
+        self._chk(self._l.pbso_group_scene_mix_clear_schedule(self._h))
+
+    def scene_mix_info(self):
+        """pbso_scene_mix_info of the first local rank that has objects (the ranks are mixed in lockstep and agree)"""
+        for rank in self.local_ranks():
+            lo, hi = self.span(rank)
+            if hi > lo:
+                return self.engine(rank).scene_mix_info()
+        raise PbsoError(capi.ERR_STATE, "scene_mix_info: no local rank has objects")
+
     def scene_fir_enable(self, n_channels, n_taps, max_onset, xfade_samples=0):
         """pbso_group_scene_fir_enable: every group step is then gathered once with GATHER_FIR"""
         self._chk(self._l.pbso_group_scene_fir_enable(self._h, n_channels, n_taps, max_onset, xfade_samples))

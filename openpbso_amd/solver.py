@@ -621,6 +621,37 @@ class Engine:
     def scene_mix_reset(self):
         self._chk(self._l.pbso_scene_mix_reset(self._h))
 
+    def scene_mix_set_at(self, t_set, gain, delay=None):
+        """pbso_scene_mix_set_at: as scene_mix_set, taking effect at the absolute sample t_set (inside a step or not)"""
+        fp = C.POINTER(C.c_float)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        c = getattr(self, "_scene_c", 0)                             # (not enabled yet: the call itself says so)
+        assert not c or (g.size == c * len(self.n_modes) and (d is None or d.size == g.size))
+        self._chk(self._l.pbso_scene_mix_set_at(self._h, int(t_set), g.ctypes.data_as(fp), None if d is None else d.ctypes.data_as(fp)))
+
+    def scene_mix_schedule(self, t_set, gain, delay=None):
+        """pbso_scene_mix_schedule: t_set [n_sets] ascending absolute samples, gain / delay [n_sets][n_channels][n_objects]; delay
+        None keeps the delays in all of them.  All or nothing."""
+        fp = C.POINTER(C.c_float)
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        d = None if delay is None else np.ascontiguousarray(delay, dtype=np.float32)
+        c = getattr(self, "_scene_c", 0)
+        assert not c or (g.size == t.size * c * len(self.n_modes) and (d is None or d.size == g.size))
+        self._chk(self._l.pbso_scene_mix_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)), g.ctypes.data_as(fp),
+                                                  None if d is None else d.ctypes.data_as(fp)))
+
+    def scene_mix_clear_schedule(self):
+        """pbso_scene_mix_clear_schedule: drops the scheduled sets not yet in force"""
+        self._chk(self._l.pbso_scene_mix_clear_schedule(self._h))
+
+    def scene_mix_info(self):
+        """pbso_scene_mix_info: t of the next mixed sample, scheduled sets still pending, mixes, sets accepted"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_mix_info(self._h, v))
+        return {"t": v[0], "pending": v[1], "mixes": v[2], "sets": v[3]}
+
     # -- scene filter mix: C channels, K taps per (channel, object) behind an integer onset (samples) per object ---------------
     def scene_fir_enable(self, n_channels, n_taps, max_onset, xfade_samples=0):
         """pbso_scene_fir_enable: from the next step on, every step is mixed exactly once (scene_fir)"""

@@ -31,6 +31,12 @@
 //                    mono one: lines <buffer> <copy> <g_0> <d_0> ... <g_{C-1}> <d_{C-1}> set copy's gain and delay (samples) per
 //                    channel from that buffer on, ramped over N samples (default 441); the tool steps the segments between
 //                    these change points, mixes each, and writes a C-channel interleaved float32 WAV (--raw: the same frames)
+//   --pan-schedule   with --pan: the pan lines are scheduled up front at sample <buffer> * frames (pbso_scene_mix_set_at; with
+//                    --devices pbso_group_scene_mix_set_at) and no longer cut the run -- the same samples in the WAV, in one step
+//                    unless another script (--retune) cuts it
+//   --time-chunks N  pbso_engine_desc::time_chunks for every engine (0, the default: the engine's policy; N > 0: every launch cut
+//                    along the time axis, N buffers per chunk; < 0: never).  With N = 1 the samples do not depend, to the last
+//                    bit, on how a script cuts the run into steps: a run with --pan-schedule is then byte for byte the run without
 //   --channels C --fir FILE [--xfade N]  the same through the scene filter mix (pbso_scene_fir; with --devices PBSO_GATHER_FIR):
 //                    lines <buffer> <copy> <onset> <taps file> give copy a filter per channel behind an onset (samples) from that
 //                    buffer on, cross-faded over N samples (default 441; change points must be at least that far apart).  A taps
@@ -220,6 +226,7 @@ struct FirDelayLine { long b; int copy; float delay; };     // --fir-delay: <buf
 struct Scene {
     int channels = 0, ramp = 441, copies = 1, max_delay = 0;
     std::vector<Pan> lines;
+    bool pan_schedule = false;                           // --pan-schedule: the lines are scheduled up front and cut nothing
     // --fir: the scene filter mix's script instead of the pan script
     bool fir = false;
     int xfade = 441, n_taps = 0, max_onset = 0;
@@ -235,7 +242,7 @@ struct Scene {
     std::vector<int> cuts(int n_buffers) const {
         std::vector<int> c{0, n_buffers};
         for (const Pan &p : lines)
-            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+            if (!pan_schedule && p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         for (const FirLine &p : fir_lines)
             if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         for (const FirDelayLine &p : fir_delay_lines)
@@ -255,6 +262,16 @@ struct Scene {
                 any = true;
             }
         return any;
+    }
+    // --pan-schedule: every buffer that has pan lines, in order, as one set at its first sample: set(t_set, gain, delay)
+    template <class Set>
+    void schedule_pan(std::vector<float> &gain, std::vector<float> &delay, Set set) const {
+        std::vector<long> at;
+        for (const Pan &p : lines) at.push_back(p.b);
+        std::sort(at.begin(), at.end());
+        at.erase(std::unique(at.begin(), at.end()), at.end());
+        for (long b : at)
+            if (set_at(b, gain, delay)) set((int64_t)b * PBSO_FRAMES_PER_BUFFER, gain.data(), delay.data());
     }
     // ... and taps [C][copies][K], onset [copies]
     bool fir_set_at(long b, std::vector<float> &taps, std::vector<int> &onset) const {
@@ -346,7 +363,8 @@ struct RetuneScript {
 // the scene on several GPUs (include/openpbso_amd.h "device group")
 static int run_group(const std::vector<int> &devices, int copies, int shift, const std::string &modes, const std::string &material,
                      const std::string &ffat, const std::vector<Hit> &hits, const std::vector<std::vector<float>> &tracks,
-                     const std::vector<Pos> &path, const StrokeScript &strokes, int n_buffers, const Scene *scene, const RetuneScript &retune, std::vector<float> &sound) {
+                     const std::vector<Pos> &path, const StrokeScript &strokes, int n_buffers, const Scene *scene, const RetuneScript &retune, int time_chunks,
+                     std::vector<float> &sound) {
     auto gcheck = [](pbso_group *g, int rc, const char *what) {
         if (rc < 0) die(std::string(what) + ": " + pbso_status_string(rc) + ": " + (g ? pbso_group_last_error(g) : ""));
     };
@@ -369,6 +387,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
     gd.n_devices = (int)devices.size();
     gd.engine.abi_version = PBSO_ABI_VERSION;
     gd.engine.qnorm_mode = PBSO_QNORM_OFF;
+    gd.engine.time_chunks = time_chunks;
     pbso_group *g = nullptr;
     gcheck(g, pbso_group_create(&gd, &g), "group_create");
     std::vector<int> mc(copies, n_aud);
@@ -440,12 +459,18 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         std::vector<float> taps(scene->fir ? (size_t)C * copies * scene->n_taps : 0, 0.f);
         std::vector<int> onset(copies, 0);
         sound.assign((size_t)C * total, 0.f);
+        if (scene->pan_schedule)
+            scene->schedule_pan(gain, delay, [&](int64_t t, const float *gn, const float *dl) {
+                gcheck(g, pbso_group_scene_mix_set_at(g, t, gn, dl), "group_scene_mix_set_at");
+            });
         const std::vector<int> cuts = retune.cut(scene->cuts(n_buffers), n_buffers);
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
             retune.apply_at(cuts[k], group_set);
             if (scene->fir) {
                 if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
                 if (scene->fir_delay_set_at(cuts[k], fir_delay)) gcheck(g, pbso_group_scene_fir_set_delay(g, fir_delay.data()), "group_scene_fir_set_delay");
+            } else if (scene->pan_schedule) {
+                // (scheduled up front)
             } else if (scene->set_at(cuts[k], gain, delay)) gcheck(g, pbso_group_scene_mix_set(g, gain.data(), delay.data()), "group_scene_mix_set");
             const int nb = cuts[k + 1] - cuts[k];
             const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
@@ -485,7 +510,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 int main(int argc, char **argv) {
     std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_delay, reverb, strokes_file, arprm_arg, retune_arg;
     StrokeScript strokes;
-    int n_buffers = 86, copies = 0, copy_shift = 1;
+    int n_buffers = 86, copies = 0, copy_shift = 1, time_chunks = 0;
     Scene scene;
     bool limit = false, pcm16 = false, master_flag = false;  // --limit; master_flag: one of its companions was given
     float limit_T = 1.f, master_gain = 1.f;
@@ -521,6 +546,8 @@ int main(int argc, char **argv) {
         else if (a == "--copy-shift") copy_shift = std::atoi(val().c_str());
         else if (a == "--channels") scene.channels = std::atoi(val().c_str());
         else if (a == "--pan") pan = val();
+        else if (a == "--pan-schedule") scene.pan_schedule = true;
+        else if (a == "--time-chunks") time_chunks = std::atoi(val().c_str());
         else if (a == "--retune") retune_arg = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else if (a == "--fir") fir = val();
@@ -732,6 +759,7 @@ int main(int argc, char **argv) {
     if (!retune_arg.empty()) retune.read(retune_arg, devices.empty() ? 1 : copies, n_buffers);
     const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
     if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
+    if (scene.pan_schedule && pan.empty()) die("--pan-schedule needs --pan FILE: it schedules that script's lines");
     if (!fir_delay.empty() && fir.empty()) die("--fir-delay needs --fir FILE: the delay sits in front of the filter mix");
     if (mixed && (scene.channels < 1 || scene.channels > 8)) die("--channels must be 1 .. 8");
     if (!fir.empty()) {
@@ -841,12 +869,13 @@ int main(int argc, char **argv) {
     const long long rs_keep = out_rate ? pbso::resample_max_out((long long)n_buffers * PBSO_FRAMES_PER_BUFFER, rs_L, rs_M) : 0;
     double device_ms = 0;
     if (!devices.empty()) {
-        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, retune, sound);
+        run_group(devices, copies, copy_shift, modes, material, ffat, hit_list, tracks, path, strokes, n_buffers, mixed ? &scene : nullptr, retune, time_chunks, sound);
     } else {
         pbso_engine_desc desc;
         std::memset(&desc, 0, sizeof(desc));
         desc.abi_version = PBSO_ABI_VERSION;
         desc.qnorm_mode = PBSO_QNORM_OFF;
+        desc.time_chunks = time_chunks;
         pbso_engine *e = nullptr;
         int rc = pbso_engine_create(&desc, &e);
         check(e, rc, "engine_create");
@@ -943,6 +972,10 @@ int main(int argc, char **argv) {
                 check(e, pbso_scene_reverb_enable(e, 1, C, scene.reverb_taps, scene.reverb_xfade), "scene_reverb_enable");
                 check(e, pbso_scene_reverb_set(e, scene.reverb.data()), "scene_reverb_set");
             }
+            if (scene.pan_schedule)
+                scene.schedule_pan(gain, delay, [&](int64_t t, const float *gn, const float *dl) {
+                    check(e, pbso_scene_mix_set_at(e, t, gn, dl), "scene_mix_set_at");
+                });
             std::vector<int> cuts = retune.cut(scene.cuts(n_buffers), n_buffers);
             if (n_tail) cuts.push_back(n_run);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
@@ -952,6 +985,8 @@ int main(int argc, char **argv) {
                 } else if (scene.fir) {
                     if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
                     if (scene.fir_delay_set_at(cuts[k], delay_now)) check(e, pbso_scene_fir_set_delay(e, delay_now.data()), "scene_fir_set_delay");
+                } else if (scene.pan_schedule) {
+                    // (scheduled up front)
                 } else if (scene.set_at(cuts[k], gain, delay)) check(e, pbso_scene_mix_set(e, gain.data(), delay.data()), "scene_mix_set");
                 const int nb = cuts[k + 1] - cuts[k];
                 const size_t row = (size_t)nb * PBSO_FRAMES_PER_BUFFER;
