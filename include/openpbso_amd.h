@@ -610,6 +610,48 @@ int pbso_scene_fir_set_delay(pbso_engine *e, const float *delay);   /* [n_object
 /* out[0] = max_delay, out[1] = ramp_samples, out[2] = the first t at which every delay ramp is over (= the next mixed t when none
  * runs), out[3] = delay sets accepted */
 int pbso_scene_fir_delay_info(pbso_engine *e, int64_t out[4]);
+/* The scene filter mix's SCHEDULE: filter sets and delay sets that take effect at absolute samples the caller gives, any number of
+ * them inside one step, so that a source that moves past a listener -- new head-related filters and a new time of flight all the
+ * time -- does not cut the run at every change point.  The two kinds of set are scheduled independently of each other.
+ * EFFECT.  A scheduled set does exactly what pbso_scene_fir_set / pbso_scene_fir_set_delay does, with t_set given by the caller
+ *   instead of "the first sample of the next mixed step".  A filter set fades in from the set in force at t_set - 1 over the
+ *   xfade_samples R of the enable, by the w(t) above; onset == NULL keeps the onsets of the set before it (0 at first).  A delay set
+ *   ramps every delay from p(t_set - 1) of the record in force at t_set - 1 (a set during a running ramp starts from the current
+ *   value), slope = (p_to - p_from) / ramp_samples divided once; z(tau) uses the record in force at tau.  The first set of a kind
+ *   after enable / reset takes effect without a fade or ramp, whichever call made it.  The output still depends on the rows, the
+ *   sets and the absolute samples at which they took effect only: a schedule mixed in one step equals, bit for bit, the same rows
+ *   cut at every t_set with pbso_scene_fir_set / pbso_scene_fir_set_delay before each piece.
+ * VALIDATION, ALL OR NOTHING.  t_set must be >= the next mixed sample (out[0] of pbso_scene_fir_schedule_info) and strictly greater
+ *   than the last pending set's of its kind (a plain set still waiting for the next mix counts as pending at the next mixed sample).
+ *   No filter set while a fade runs: against its predecessor, pending or in force, a filter set needs t_set - t_prev + 1 >= R
+ *   whenever there is a predecessor and R >= 2 (out[3] is the smallest t_set that passes); delay sets may follow each other at any
+ *   spacing.  Taps, onsets and delays are validated as the plain calls validate them.  Otherwise PBSO_ERR_INVALID.  The *_schedule
+ *   calls validate all of their sets before they take any: a refused call changes nothing.  PBSO_ERR_STATE before the enable, and
+ *   for a delay set before pbso_scene_fir_delay_enable.  n_sets == 0 is accepted.
+ * LIFETIME.  A set scheduled beyond the next step stays pending until the step that contains it.  At most 4096 filter sets and
+ *   65 536 delay sets may take effect inside one mixed step: with more, pbso_scene_fir returns PBSO_ERR_INVALID and nothing has
+ *   changed (step in shorter pieces, or clear the schedule).  If the device memory for a step's sets -- a pool of S + 2 padded
+ *   filter sets of C * n_objects * LP floats, LP = (K + 22) / 8 * 8 + 16, and K_d + 1 blocks of n_objects * 32 bytes of delay
+ *   records -- cannot be allocated, pbso_scene_fir returns PBSO_ERR_NOMEM and nothing has changed.  A step without a scheduled
+ *   set inside it is launched exactly as without a schedule.
+ * WITH pbso_scene_fir_set / pbso_scene_fir_set_delay.  While scheduled sets of its kind are pending the plain set returns
+ *   PBSO_ERR_STATE; with none pending it behaves exactly as without a schedule.  After a drained schedule it continues from what
+ *   the schedule left, mid-fade (refused until the fade is over, as ever) or mid-ramp included: as if every scheduled set had been
+ *   a plain set between two steps cut at its sample.  (A plain delay set then waits for the mix that took the last scheduled delay
+ *   sets, not for more.)
+ * pbso_scene_fir_clear_schedule drops the pending filter AND delay sets not yet in force.  pbso_scene_fir_reset and a new
+ *   pbso_scene_fir_enable drop them too; the reset keeps the delays last IN FORCE, ramps finished.
+ * pbso_scene_fir_schedule_info: out[0] = t of the next mixed sample, out[1] = scheduled filter sets pending, out[2] = scheduled delay
+ *   sets pending, out[3] = the smallest t_set the next scheduled filter set may have.  pbso_scene_fir_info out[3] and
+ *   pbso_scene_fir_delay_info out[3] count every set of a *_schedule call.                                                    */
+int pbso_scene_fir_set_at(pbso_engine *e, int64_t t_set, const float *taps /* [C][n_objects][K] */, const int *onset /* [n_objects] or NULL = unchanged */);
+int pbso_scene_fir_schedule(pbso_engine *e, int n_sets, const int64_t *t_set,
+                            const float *taps /* [n_sets][C][n_objects][K] */,
+                            const int *onset  /* [n_sets][n_objects], or NULL = unchanged by all of them */);
+int pbso_scene_fir_set_delay_at(pbso_engine *e, int64_t t_set, const float *delay /* [n_objects] */);
+int pbso_scene_fir_delay_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const float *delay /* [n_sets][n_objects] */);
+int pbso_scene_fir_clear_schedule(pbso_engine *e);      /* drops the pending filter AND delay sets not yet in force */
+int pbso_scene_fir_schedule_info(pbso_engine *e, int64_t out[4]);
 
 /* Scene reverb: a bus effect behind the mixers -- n_in device-resident signals (a send bus: what pbso_mix_objects, pbso_scene_mix
  * or pbso_scene_fir just wrote, or some of their channels) convolved with a long impulse response per (output channel, input),
@@ -851,6 +893,15 @@ int pbso_group_scene_fir_set(pbso_group *g, const float *taps, const int *onset)
  * again, which drops the stage on every rank, puts the group back in one state. */
 int pbso_group_scene_fir_delay_enable(pbso_group *g, int max_delay, int ramp_samples);
 int pbso_group_scene_fir_set_delay(pbso_group *g, const float *delay);
+/* ... and the filter mix's schedule on every local rank: taps [n_sets][C][n_objects of the whole job][K], onset and delay
+ * [n_sets][n_objects of the whole job] by global id, each rank taking its slice of every set.  The values are checked for the
+ * whole job before any rank takes a set; the times are checked by the ranks' engines, which are mixed in lockstep and hold one
+ * clock (pbso_scene_fir_schedule_info of any pbso_group_engine has the counts).                                              */
+int pbso_group_scene_fir_set_at(pbso_group *g, int64_t t_set, const float *taps, const int *onset);
+int pbso_group_scene_fir_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *taps, const int *onset);
+int pbso_group_scene_fir_set_delay_at(pbso_group *g, int64_t t_set, const float *delay);
+int pbso_group_scene_fir_delay_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *delay);
+int pbso_group_scene_fir_clear_schedule(pbso_group *g);
 /* the last gather's result on a local rank, a device pointer: ALL -> [world_size * rows_per_rank][n_buffers * 513] (rank r's
  * objects from row r * rows_per_rank; shards smaller than the largest are padded with silent rows), ROOT -> the same on rank 0
  * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE and FIR -> [C][n_buffers * 513].  rows / row_floats (may be NULL)

@@ -39,6 +39,11 @@ EXPORTS = [
     # ... and its delay stage (a ramped fractional delay per object in front of the filters)
     "pbso_scene_fir_delay_enable", "pbso_scene_fir_set_delay", "pbso_scene_fir_delay_info",
     "pbso_group_scene_fir_delay_enable", "pbso_group_scene_fir_set_delay",
+    # ... and the schedule of its filter and delay sets (sets that take effect at absolute samples, any number inside one step)
+    "pbso_scene_fir_set_at", "pbso_scene_fir_schedule", "pbso_scene_fir_set_delay_at", "pbso_scene_fir_delay_schedule",
+    "pbso_scene_fir_clear_schedule", "pbso_scene_fir_schedule_info",
+    "pbso_group_scene_fir_set_at", "pbso_group_scene_fir_schedule", "pbso_group_scene_fir_set_delay_at",
+    "pbso_group_scene_fir_delay_schedule", "pbso_group_scene_fir_clear_schedule",
     # the scene reverb (n_in bus signals through K taps, up to 1 << 17, per output channel and input)
     "pbso_scene_reverb_enable", "pbso_scene_reverb_set", "pbso_scene_reverb", "pbso_read_scene_reverb", "pbso_scene_reverb_reset",
     "pbso_scene_reverb_info",
@@ -251,6 +256,19 @@ def lib():
         l.pbso_scene_fir_delay_info.argtypes = [vp, C.POINTER(C.c_int64)]
         l.pbso_group_scene_fir_delay_enable.argtypes = [vp, C.c_int, C.c_int]
         l.pbso_group_scene_fir_set_delay.argtypes = [vp, fp]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_fir_schedule"):
+        tp = C.POINTER(C.c_int64)
+        l.pbso_scene_fir_set_at.argtypes = [vp, C.c_int64, fp, ip]
+        l.pbso_scene_fir_schedule.argtypes = [vp, C.c_int, tp, fp, ip]
+        l.pbso_scene_fir_set_delay_at.argtypes = [vp, C.c_int64, fp]
+        l.pbso_scene_fir_delay_schedule.argtypes = [vp, C.c_int, tp, fp]
+        l.pbso_scene_fir_clear_schedule.argtypes = [vp]
+        l.pbso_scene_fir_schedule_info.argtypes = [vp, tp]
+        l.pbso_group_scene_fir_set_at.argtypes = [vp, C.c_int64, fp, ip]
+        l.pbso_group_scene_fir_schedule.argtypes = [vp, C.c_int, tp, fp, ip]
+        l.pbso_group_scene_fir_set_delay_at.argtypes = [vp, C.c_int64, fp]
+        l.pbso_group_scene_fir_delay_schedule.argtypes = [vp, C.c_int, tp, fp]
+        l.pbso_group_scene_fir_clear_schedule.argtypes = [vp]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_reverb"):
         l.pbso_scene_reverb_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         l.pbso_scene_reverb_set.argtypes = [vp, fp]

@@ -1,7 +1,8 @@
 // What the engine's sides of the scene buses (scene_mix.cpp, scene_fir.cpp, scene_reverb.cpp, master.cpp) have in common, and
 // nothing of what is particular to one: device and pinned memory that frees itself, the exact-size grow, the double-buffered
-// history, the ring of pinned uploads, the engine-owned output, and (bus_clock.h, free of HIP) the step clock, the cross-fade
-// clock and the ramp.  Included by those four files only; a bus knows this header and none of the other buses.
+// history, the ring of pinned uploads, the growable staging of a step's scheduled sets, the engine-owned output, and
+// (bus_clock.h, free of HIP) the step clock, the cross-fade clock and the ramp.  Included by those four files only; a bus knows
+// this header and none of the other buses.
 //
 // A bus's struct is freed behind a synchronisation of the stream (its *_release), or before anything was launched on its
 // memory (a failed enable, where the struct leaves its scope).
@@ -122,6 +123,49 @@ struct UploadRing {
         if (e != hipSuccess) return e;
         used[slot] = true;
         slot = (slot + 1) % UP_SLOTS;
+        return hipSuccess;
+    }
+};
+
+// Pinned staging of one step's scheduled sets (the scene mix's and the filter mix's schedules), in a ring as UploadRing, but each
+// slot grows to what a step needs.  A slot is rewritten (or freed for a larger one) only once the copy that last read it is done.
+struct StagingRing {
+    static constexpr int SLOTS = UploadRing::UP_SLOTS;
+    char *block[SLOTS] = {};
+    size_t cap[SLOTS] = {};
+    hipEvent_t ev[SLOTS] = {};
+    bool used[SLOTS] = {};
+    int slot = 0;
+    StagingRing() = default;
+    StagingRing(const StagingRing &) = delete;
+    StagingRing &operator=(const StagingRing &) = delete;
+    ~StagingRing() {
+        for (int i = 0; i < SLOTS; ++i) {
+            if (block[i]) (void)hipHostFree(block[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+    // the next slot's block, at least `bytes` long, once its last copy has left it
+    hipError_t acquire(size_t bytes, char *&b) {
+        hipError_t e = hipSuccess;
+        if (!ev[slot] && (e = hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming)) != hipSuccess) { ev[slot] = nullptr; return e; }
+        if (used[slot] && (e = hipEventSynchronize(ev[slot])) != hipSuccess) return e;
+        used[slot] = false;
+        if (cap[slot] < bytes) {
+            if (block[slot]) (void)hipHostFree(block[slot]);
+            block[slot] = nullptr;
+            cap[slot] = 0;
+            if ((e = hipHostMalloc((void **)&block[slot], bytes, hipHostMallocDefault)) != hipSuccess) { block[slot] = nullptr; return e; }
+            cap[slot] = bytes;
+        }
+        b = block[slot];
+        return hipSuccess;
+    }
+    hipError_t record(hipStream_t s) {
+        const hipError_t e = hipEventRecord(ev[slot], s);
+        if (e != hipSuccess) return e;
+        used[slot] = true;
+        slot = (slot + 1) % SLOTS;
         return hipSuccess;
     }
 };

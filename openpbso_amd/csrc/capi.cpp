@@ -575,6 +575,48 @@ int pbso_scene_fir_set_delay(pbso_engine *e, const float *delay) {
     GUARD_END(e)
 }
 
+int pbso_scene_fir_set_at(pbso_engine *e, int64_t t_set, const float *taps, const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_schedule("scene_fir_set_at", 1, &t_set, taps, onset);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const float *taps, const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_schedule("scene_fir_schedule", n_sets, t_set, taps, onset);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_set_delay_at(pbso_engine *e, int64_t t_set, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_delay_schedule("scene_fir_set_delay_at", 1, &t_set, delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_delay_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const float *delay) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_delay_schedule("scene_fir_delay_schedule", n_sets, t_set, delay);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_clear_schedule(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_clear_schedule();
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_schedule_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_schedule_info(out);
+    GUARD_END(e)
+}
+
 int pbso_scene_fir_delay_info(pbso_engine *e, int64_t out[4]) {
     NEED(e);
     GUARD_BEGIN

@@ -278,6 +278,12 @@ public:
     int scene_fir_delay_enable(int max_delay, int ramp_samples);
     int scene_fir_set_delay(const float *delay);
     int scene_fir_delay_info(int64_t out[4]);
+    // ... and the schedule of both kinds of set: sets that take effect at absolute samples given by the caller (kernels_fir_sched.hip;
+    // `call`: the entry point, for the messages)
+    int scene_fir_schedule(const char *call, int n_sets, const int64_t *t_set, const float *taps, const int *onset);
+    int scene_fir_delay_schedule(const char *call, int n_sets, const int64_t *t_set, const float *delay);
+    int scene_fir_clear_schedule();
+    int scene_fir_schedule_info(int64_t out[4]);
     // the scene reverb (scene_reverb.cpp, kernels_reverb.hip): a caller's n_in bus signals through K taps per (output channel, input)
     int scene_reverb_enable(int n_in, int n_out, int n_taps, int xfade_samples);
     int scene_reverb_set(const float *taps);
@@ -573,6 +579,7 @@ private:
     void scene_mix_release();
     SceneFir *fir_ = nullptr;                            // pbso_scene_fir_enable
     void scene_fir_release();
+    int scene_fir_scheduled_step(void *d_out);          // pbso_scene_fir of a step with scheduled sets inside it
     SceneReverb *reverb_ = nullptr;                      // pbso_scene_reverb_enable
     void scene_reverb_release();
     Master *master_ = nullptr;                           // pbso_master_enable

@@ -675,6 +675,92 @@ int pbso_group_scene_fir_set_delay(pbso_group *g, const float *delay) {
     return PBSO_OK;
 }
 
+// the filter mix's schedule: every rank takes the slice of its own objects of every set.  The values are checked for the whole
+// job first; the times are checked by the engines, which are mixed in lockstep and so hold one clock and one pending list: the
+// first rank's refusal is every rank's, and no rank has taken anything by then.
+static int group_scene_fir_schedule(pbso_group *g, const char *call, int n_sets, const int64_t *t_set, const float *taps, const int *onset) {
+    const std::string name(call);
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, name + ": the group's scene filter mix is not enabled");
+    if (n_sets < 0) return gfail(g, PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return gfail(g, PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!taps) return gfail(g, PBSO_ERR_INVALID, name + ": taps is NULL");
+    const size_t n = (size_t)g->n_objects, K = (size_t)g->fir_k, C = (size_t)g->fir_c;
+    for (size_t i = 0; i < (size_t)n_sets * C * n * K; ++i)
+        if (!std::isfinite(taps[i])) return gfail(g, PBSO_ERR_INVALID, name + ": a tap is not finite");
+    if (onset)
+        for (size_t i = 0; i < (size_t)n_sets * n; ++i)
+            if (onset[i] < 0 || onset[i] > g->fir_max_onset) return gfail(g, PBSO_ERR_INVALID, name + ": an onset is outside [0, max_onset]");
+    try {
+        std::vector<float> ts;
+        std::vector<int> os;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local;
+            ts.resize((size_t)n_sets * C * nl * K);
+            os.resize(onset ? (size_t)n_sets * nl : 0);
+            for (size_t k = 0; k < (size_t)n_sets; ++k) {
+                for (size_t c = 0; c < C; ++c)
+                    std::copy(taps + ((k * C + c) * n + lo) * K, taps + ((k * C + c) * n + lo + nl) * K, ts.begin() + (k * C + c) * nl * K);
+                if (onset) std::copy(onset + k * n + lo, onset + k * n + lo + nl, os.begin() + k * nl);
+            }
+            GENG(g, rk, pbso_scene_fir_schedule(rk.eng, n_sets, t_set, ts.data(), onset ? os.data() : nullptr));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
+    return PBSO_OK;
+}
+
+static int group_scene_fir_delay_schedule(pbso_group *g, const char *call, int n_sets, const int64_t *t_set, const float *delay) {
+    const std::string name(call);
+    if (!g || !g->fir_on || !g->fir_delay_on) return gfail(g, PBSO_ERR_STATE, name + ": the group's delay stage is not enabled");
+    if (n_sets < 0) return gfail(g, PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return gfail(g, PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!delay) return gfail(g, PBSO_ERR_INVALID, name + ": delay is NULL");
+    const size_t n = (size_t)g->n_objects;
+    for (size_t i = 0; i < (size_t)n_sets * n; ++i)
+        if (!(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)g->fir_max_delay))
+            return gfail(g, PBSO_ERR_INVALID, name + ": a delay is not finite or outside [0, max_delay]");
+    try {
+        std::vector<float> ds;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local;
+            ds.resize((size_t)n_sets * nl);
+            for (size_t k = 0; k < (size_t)n_sets; ++k) std::copy(delay + k * n + lo, delay + k * n + lo + nl, ds.begin() + k * nl);
+            GENG(g, rk, pbso_scene_fir_delay_schedule(rk.eng, n_sets, t_set, ds.data()));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
+    return PBSO_OK;
+}
+
+int pbso_group_scene_fir_set_at(pbso_group *g, int64_t t_set, const float *taps, const int *onset) {
+    return group_scene_fir_schedule(g, "scene_fir_set_at", 1, &t_set, taps, onset);
+}
+
+int pbso_group_scene_fir_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *taps, const int *onset) {
+    return group_scene_fir_schedule(g, "scene_fir_schedule", n_sets, t_set, taps, onset);
+}
+
+int pbso_group_scene_fir_set_delay_at(pbso_group *g, int64_t t_set, const float *delay) {
+    return group_scene_fir_delay_schedule(g, "scene_fir_set_delay_at", 1, &t_set, delay);
+}
+
+int pbso_group_scene_fir_delay_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *delay) {
+    return group_scene_fir_delay_schedule(g, "scene_fir_delay_schedule", n_sets, t_set, delay);
+}
+
+int pbso_group_scene_fir_clear_schedule(pbso_group *g) {
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, "scene_fir_clear_schedule: the group's scene filter mix is not enabled");
+    for (Rank &rk : g->ranks)
+        if (rk.n_local > 0) GENG(g, rk, pbso_scene_fir_clear_schedule(rk.eng));
+    return PBSO_OK;
+}
+
 // point-to-point transfers in pieces of at most 256 MB: a 1.8 GB ncclSend / ncclRecv pair of a rank to itself (1024 objects x ten seconds
 // of audio) came back WRONG on RCCL 2.26.6 while 0.45 GB was right (profiles/r05 bench_1rank.err); sender and receiver cut alike
 static constexpr size_t P2P_MAX = (size_t)64 << 20;      // floats

@@ -391,6 +391,29 @@ int launch_scene_fir_delay(const float *rows, int n_obj, long long n, const floa
                            const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0, long long t_set, int R,
                            float *parts, float *out, hipStream_t stream);
 
+// The same step with scheduled sets taking effect inside it (pbso_scene_fir_schedule / _delay_schedule; kernels_fir_sched.hip).
+// The step's filter sets lie in a pool: [S + 2] sets of padded reversed taps [C][n_obj][LP] with onsets [S + 2][n_obj], 0 / 1 the
+// set in force / faded out when the step begins (have_to0 / have_from0, since t_set0), 2 + k the set that takes effect at the
+// ascending absolute sample t_f[k] in [t0, t0 + n).  strips: the step's work strips (fir_schedule.h) of at most `strip` samples,
+// scene_fir_sched_strip(n, n_obj) of them; any_from: one of them has a set_from.  parts as launch_scene_fir's.
+// params non-null: the delay stage.  Kd >= 0 delay sets at the ascending t_d[Kd] in the step, targets [Kd][n_obj] f32;
+// fir_delay_expand_kernel chains ramp_next over them: rec [Kd + 1][n_obj], block 0 = params as they are, block k + 1 in force
+// from t_d[k] on; params becomes the last block.  any_set 0: delay set 0 is the first after enable / reset (no ramp).
+constexpr int SCENE_FIR_MAX_SETS_PER_STEP = 4096;
+struct FirStrip;
+struct FirSchedStep {
+    const float *rows; int n_obj; long long n;
+    const float *hist; float *hist_next; int H;          // of x, or of z with the delay stage
+    const float *hist_x; float *hist_x_next; int Hx;     // the delay stage's
+    SceneParam *params, *rec; const long long *t_d; const float *targets; int Kd, Rd, any_set;
+    const float *pool; const int *onpool; const long long *t_f; int S, have_to0, have_from0; long long t_set0;
+    const FirStrip *strips; int n_strips, strip, any_from;
+    int C, K, R; long long t0;
+    float *parts, *out;
+};
+int scene_fir_sched_strip(long long n, int n_obj);
+int launch_scene_fir_sched(const FirSchedStep &a, hipStream_t stream);
+
 // pbso_scene_reverb (kernels_reverb.hip): n_in bus signals convolved with K f32 taps per (output channel, input), the taps cut into
 // segments of SCENE_REVERB_SEGMENT: one fmaf chain per (channel, input, segment, sample) on the f32 MFMA, the segments' rows then
 // in (input, segment) order.

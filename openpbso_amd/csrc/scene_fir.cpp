@@ -3,12 +3,18 @@
 // the device, and the rule that every step is mixed exactly once.  It reads what a step left (last_audio_, last_nb_) and counts
 // steps by tot_steps_.  It knows bus_state.h, which holds what the buses have in common (the cross-fade's clock among it), and
 // nothing of the other buses.
+// The schedule (pbso_scene_fir_schedule, pbso_scene_fir_delay_schedule; kernels_fir_sched.hip): the filter and delay sets not yet in
+// force wait on the host as given, each with its t_set; a mix takes those inside its step to the device in one staged block, cuts
+// the step into work strips (fir_schedule.h) and launches the schedule's kernels.  A step without a scheduled set inside it is
+// launched as it always was.
 // The optional delay stage (pbso_scene_fir_delay_enable; kernels_fir_delay.hip) puts the scene mix's ramped fractional delay per
 // object in front of the filters: its records, the second history (of x: `hist` then holds z), and the other launch.
 #include "bus_state.h"
+#include "fir_schedule.h"
 
 #include <cmath>
 #include <cstring>
+#include <deque>
 
 namespace pbso {
 
@@ -23,6 +29,31 @@ struct FirDelay {
     HistPair hist_x;                                     // [N][Hx]
     DevMem<SceneParam> d_p;
     UploadRing up;                                       // blocks of N records
+    // the schedule: the delay sets not yet in force, ascending in t and none before the clock.  A mix expands those inside its step
+    // into the step's records on the device (fir_delay_expand_kernel), and the last block becomes d_p; p then lags behind d_p
+    // (p_stale) until the copy back, queued behind the mix, is taken over -- the scene mix's mechanism.
+    struct Pending { long long t; std::vector<float> v; };
+    std::deque<Pending> sched;
+    DevMem<SceneParam> d_rec;                            // the step's records [K_d + 1][N]
+    SceneParam *p_back = nullptr;                        // pinned: d_p after the last mix that took scheduled sets
+    hipEvent_t ev_back = nullptr;
+    bool p_stale = false;
+    FirDelay() = default;
+    FirDelay(const FirDelay &) = delete;
+    FirDelay &operator=(const FirDelay &) = delete;
+    ~FirDelay() {
+        if (p_back) (void)hipHostFree(p_back);
+        if (ev_back) (void)hipEventDestroy(ev_back);
+    }
+    // p as the device has it, before anything reads or changes it: waits for the mix that took the scheduled sets, not for more
+    hipError_t refresh() {
+        if (!p_stale) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev_back);
+        if (e != hipSuccess) return e;
+        std::memcpy(p.data(), p_back, p.size() * sizeof(SceneParam));
+        p_stale = false;
+        return hipSuccess;
+    }
     // the first t at which every ramp is over; t itself when none runs
     long long ramp_end(long long t) const { return ramping && t - t_set + 1 < (long long)ramp ? t_set + ramp - 1 : t; }
 };
@@ -45,6 +76,14 @@ struct SceneFir {
     DevMem<float> d_P[2], d_raw;
     DevMem<int> d_onset[2];
     UploadRing up;                                       // blocks of taps [C][N][K], then onsets [N]
+    // the schedule: the filter sets not yet in force as given (onset NULL resolved to the predecessor's), ascending in t, none
+    // before the clock and none inside its predecessor's fade
+    struct Pending { long long t; std::vector<float> taps; std::vector<int> onset; };
+    std::deque<Pending> sched;
+    StagingRing stage;                                   // a step's times, work strips, onsets, delays and taps
+    DevMem<char> d_sets;                                 // ... on the device
+    DevMem<float> d_pool;                                // the step's pool of padded reversed taps [S + 2][C][N][LP]
+    DevMem<int> d_onpool;                                // ... and onsets [S + 2][N]
 
     size_t taps_floats() const { return (size_t)C * N * K; }
 };
@@ -104,6 +143,7 @@ int Engine::scene_fir_set(const float *taps, const int *onset) {
     if (!fir_) return fail(PBSO_ERR_STATE, "scene_fir_set: the scene filter mix is not enabled");
     if (!taps) return fail(PBSO_ERR_INVALID, "scene_fir_set: taps is NULL");
     SceneFir &m = *fir_;
+    if (!m.sched.empty()) return fail(PBSO_ERR_STATE, "scene_fir_set: scheduled sets are pending (pbso_scene_fir_clear_schedule drops them)");
     if (m.fade.fading(m.clock.t))
         return fail(PBSO_ERR_STATE, "scene_fir_set: the cross-fade of the last set is still running (pbso_scene_fir_info tells when it ends)");
     const size_t nt = m.taps_floats();
@@ -130,6 +170,10 @@ int Engine::scene_fir(void *d_out) {
     HIPTRY(hipSetDevice(desc_.device));
     const long long n = (long long)last_nb_ * B_;
     const int groups = mix_objects_groups(m.N);
+    // a step with scheduled sets inside it (none lies before it) goes to the schedule's kernels; any other is launched as ever
+    if ((!m.sched.empty() && m.sched.front().t < m.clock.t + n) ||
+        (m.delay && !m.delay->sched.empty() && m.delay->sched.front().t < m.clock.t + n))
+        return scene_fir_scheduled_step(d_out);
     float *out;
     GROWTRY(m.out.resolve(d_out, (size_t)m.C * n, stream_, out), "scene_fir: cannot allocate the output", "scene_fir: output");
     GROWTRY(grow(m.parts, (size_t)2 * m.C * groups * n, stream_), "scene_fir: cannot allocate the partial rows", "scene_fir: partial rows");
@@ -159,6 +203,7 @@ int Engine::scene_fir(void *d_out) {
     //  effect on the host and is not pending again; the caller's way on from a failed mix is the reset)
     FirDelay *d = m.delay.get();
     if (d && d->have_pend) {                             // the set takes effect at t, by the scene mix's rule
+        HIPTRY(d->refresh());                            // (after a drained schedule: from the value it left, mid-ramp included)
         for (int o = 0; o < m.N; ++o) ramp_set(d->p[o], d->pend[o], t, d->ramp, d->any_set);
         d->ramping = d->any_set && d->ramp > 0;
         d->t_set = t;
@@ -200,8 +245,11 @@ int Engine::scene_fir_reset() {
     SceneFir &m = *fir_;
     HIPTRY(hipSetDevice(desc_.device));
     HIPTRY(m.hist.reset(stream_));
+    m.sched.clear();                                     // (the schedule is dropped: the delays last IN FORCE stay)
     if (FirDelay *d = m.delay.get()) {                   // both histories; the delays stay at their targets, ramps finished
+        HIPTRY(d->refresh());
         HIPTRY(d->hist_x.reset(stream_));
+        d->sched.clear();
         if (d->have_pend)
             for (int o = 0; o < m.N; ++o) d->p[o].to = d->pend[o];
         for (SceneParam &q : d->p) ramp_settle(q);
@@ -256,6 +304,14 @@ int Engine::scene_fir_delay_enable(int max_delay, int ramp) {
     case UploadRing::NO_EVENT: return hip_fail(hipErrorInvalidValue, "scene_fir_delay_enable: hipEventCreate");
     case UploadRing::OK: break;
     }
+    if (hipHostMalloc((void **)&d->p_back, d->p.size() * sizeof(SceneParam), hipHostMallocDefault) != hipSuccess) {
+        d->p_back = nullptr;
+        return nomem("the delays");
+    }
+    if (hipEventCreateWithFlags(&d->ev_back, hipEventDisableTiming) != hipSuccess) {
+        d->ev_back = nullptr;
+        return hip_fail(hipErrorInvalidValue, "scene_fir_delay_enable: hipEventCreate");
+    }
     m.delay = std::move(d);
     return PBSO_OK;
 }
@@ -264,6 +320,7 @@ int Engine::scene_fir_set_delay(const float *delay) {
     if (!fir_ || !fir_->delay) return fail(PBSO_ERR_STATE, "scene_fir_set_delay: the delay stage is not enabled (pbso_scene_fir_delay_enable)");
     if (!delay) return fail(PBSO_ERR_INVALID, "scene_fir_set_delay: delay is NULL");
     FirDelay &d = *fir_->delay;
+    if (!d.sched.empty()) return fail(PBSO_ERR_STATE, "scene_fir_set_delay: scheduled sets are pending (pbso_scene_fir_clear_schedule drops them)");
     for (int o = 0; o < fir_->N; ++o)
         if (!(std::isfinite(delay[o]) && delay[o] >= 0.f && delay[o] <= (float)d.max_delay))
             return fail(PBSO_ERR_INVALID, "scene_fir_set_delay: a delay is not finite or outside [0, max_delay]");
@@ -282,6 +339,257 @@ int Engine::scene_fir_delay_info(int64_t out[4]) {
     out[1] = d.ramp;
     out[2] = d.ramp_end(fir_->clock.t);
     out[3] = d.n_sets;
+    return PBSO_OK;
+}
+
+// ---- the schedule
+
+// what a scheduled filter set comes behind: the last pending one, else a plain set waiting for the next mix (it takes effect at
+// the clock), else the set in force.  floor: the smallest t_set that is not before the clock and ascending.
+struct FirPredecessor { bool have; long long t, floor; };
+static FirPredecessor fir_predecessor(const SceneFir &m) {
+    if (!m.sched.empty()) return {true, m.sched.back().t, m.sched.back().t + 1};
+    if (m.fade.pending) return {true, m.clock.t, m.clock.t + 1};
+    return {m.fade.have_to, m.fade.t_set, m.clock.t};
+}
+static long long fir_delay_floor(const SceneFir &m, const FirDelay &d) {
+    return !d.sched.empty() ? d.sched.back().t + 1 : (d.have_pend ? m.clock.t + 1 : m.clock.t);
+}
+
+// n_sets filter sets at the absolute samples t_set, taps [n_sets][C][N][K], onset [n_sets][N] or NULL (unchanged by all of them);
+// `call` names the entry point in the messages.  All of them are checked before the first is taken.
+int Engine::scene_fir_schedule(const char *call, int n_sets, const int64_t *t_set, const float *taps, const int *onset) {
+    const std::string name(call);
+    if (!fir_) return fail(PBSO_ERR_STATE, name + ": the scene filter mix is not enabled");
+    if (n_sets < 0) return fail(PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return fail(PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!taps) return fail(PBSO_ERR_INVALID, name + ": taps is NULL");
+    SceneFir &m = *fir_;
+    FirPredecessor prev = fir_predecessor(m);
+    for (int k = 0; k < n_sets; ++k) {
+        const long long t = (long long)t_set[k];
+        if (t < m.clock.t) return fail(PBSO_ERR_INVALID, name + ": a t_set lies before the next mixed sample");
+        if (t < prev.floor) return fail(PBSO_ERR_INVALID, name + ": the t_set are not ascending behind the last pending set's");
+        if (prev.have && !fir_spacing_ok(t, prev.t, m.fade.R))
+            return fail(PBSO_ERR_INVALID, name + ": a t_set lies inside the cross-fade of the set before it (pbso_scene_fir_schedule_info tells the first that may follow)");
+        prev = {true, t, t + 1};
+    }
+    const size_t nt = m.taps_floats();
+    for (size_t i = 0; i < (size_t)n_sets * nt; ++i)
+        if (!std::isfinite(taps[i])) return fail(PBSO_ERR_INVALID, name + ": a tap is not finite");
+    if (onset)
+        for (size_t i = 0; i < (size_t)n_sets * m.N; ++i)
+            if (onset[i] < 0 || onset[i] > m.max_onset) return fail(PBSO_ERR_INVALID, name + ": an onset is outside [0, max_onset]");
+    std::deque<SceneFir::Pending> taken;                 // (built apart: a failed allocation leaves the pending list as it was)
+    // onset NULL keeps the onsets of the set before (0 at first)
+    const std::vector<int> *on_prev = !m.sched.empty() ? &m.sched.back().onset : (m.fade.pending ? &m.pend_onset : &m.onset_to);
+    for (int k = 0; k < n_sets; ++k) {
+        SceneFir::Pending q{(long long)t_set[k], {}, {}};
+        q.taps.assign(taps + (size_t)k * nt, taps + (size_t)(k + 1) * nt);
+        if (onset) q.onset.assign(onset + (size_t)k * m.N, onset + (size_t)(k + 1) * m.N);
+        else q.onset = *on_prev;
+        taken.push_back(std::move(q));
+        on_prev = &taken.back().onset;
+    }
+    for (SceneFir::Pending &q : taken) m.sched.push_back(std::move(q));
+    m.n_sets += n_sets;
+    return PBSO_OK;
+}
+
+int Engine::scene_fir_delay_schedule(const char *call, int n_sets, const int64_t *t_set, const float *delay) {
+    const std::string name(call);
+    if (!fir_ || !fir_->delay) return fail(PBSO_ERR_STATE, name + ": the delay stage is not enabled (pbso_scene_fir_delay_enable)");
+    if (n_sets < 0) return fail(PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!t_set) return fail(PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!delay) return fail(PBSO_ERR_INVALID, name + ": delay is NULL");
+    SceneFir &m = *fir_;
+    FirDelay &d = *m.delay;
+    long long floor = fir_delay_floor(m, d);
+    for (int k = 0; k < n_sets; ++k) {
+        const long long t = (long long)t_set[k];
+        if (t < m.clock.t) return fail(PBSO_ERR_INVALID, name + ": a t_set lies before the next mixed sample");
+        if (t < floor) return fail(PBSO_ERR_INVALID, name + ": the t_set are not ascending behind the last pending set's");
+        floor = t + 1;
+    }
+    for (size_t i = 0; i < (size_t)n_sets * m.N; ++i)
+        if (!(std::isfinite(delay[i]) && delay[i] >= 0.f && delay[i] <= (float)d.max_delay))
+            return fail(PBSO_ERR_INVALID, name + ": a delay is not finite or outside [0, max_delay]");
+    std::deque<FirDelay::Pending> taken;
+    for (int k = 0; k < n_sets; ++k) {
+        FirDelay::Pending q{(long long)t_set[k], {}};
+        q.v.assign(delay + (size_t)k * m.N, delay + (size_t)(k + 1) * m.N);
+        taken.push_back(std::move(q));
+    }
+    for (FirDelay::Pending &q : taken) d.sched.push_back(std::move(q));
+    d.n_sets += n_sets;
+    return PBSO_OK;
+}
+
+int Engine::scene_fir_clear_schedule() {
+    if (!fir_) return fail(PBSO_ERR_STATE, "scene_fir_clear_schedule: the scene filter mix is not enabled");
+    fir_->sched.clear();
+    if (fir_->delay) fir_->delay->sched.clear();
+    return PBSO_OK;
+}
+
+int Engine::scene_fir_schedule_info(int64_t out[4]) {
+    if (!fir_) return fail(PBSO_ERR_STATE, "scene_fir_schedule_info: the scene filter mix is not enabled");
+    if (!out) return fail(PBSO_ERR_INVALID, "scene_fir_schedule_info: out is NULL");
+    const SceneFir &m = *fir_;
+    const FirPredecessor prev = fir_predecessor(m);
+    out[0] = m.clock.t;
+    out[1] = (int64_t)m.sched.size();
+    out[2] = m.delay ? (int64_t)m.delay->sched.size() : 0;
+    out[3] = fir_next_t_min(prev.floor, prev.have, prev.t, m.fade.R);
+    return PBSO_OK;
+}
+
+// A step with scheduled sets inside it.  A plain set still waiting for this mix takes effect at the step's first sample: it goes
+// in front of the scheduled ones (which lie behind it) as one more set of its kind.  Everything that can refuse comes before
+// anything is taken or launched.
+int Engine::scene_fir_scheduled_step(void *d_out) {
+    SceneFir &m = *fir_;
+    FirDelay *d = m.delay.get();
+    XFade &f = m.fade;
+    const long long n = (long long)last_nb_ * B_, t = m.clock.t;
+    const int groups = mix_objects_groups(m.N);
+    size_t Ss = 0, Ks = 0;                               // the scheduled sets inside the step
+    while (Ss < m.sched.size() && m.sched[Ss].t < t + n) ++Ss;
+    if (d) while (Ks < d->sched.size() && d->sched[Ks].t < t + n) ++Ks;
+    const size_t S = Ss + (f.pending ? 1 : 0), Kd = Ks + (d && d->have_pend ? 1 : 0);
+    if (S > (size_t)SCENE_FIR_MAX_SETS_PER_STEP)
+        return fail(PBSO_ERR_INVALID, "scene_fir: more than 4096 filter sets take effect inside this step (step in shorter pieces, or pbso_scene_fir_clear_schedule)");
+    if (Kd > (size_t)SCENE_MAX_SETS_PER_STEP)
+        return fail(PBSO_ERR_INVALID, "scene_fir: more than 65536 delay sets take effect inside this step (step in shorter pieces, or pbso_scene_fir_clear_schedule)");
+    // the step's times and its work strips
+    std::vector<long long> t_f, t_d;
+    if (f.pending) t_f.push_back(t);
+    for (size_t k = 0; k < Ss; ++k) t_f.push_back(m.sched[k].t);
+    if (d && d->have_pend) t_d.push_back(t);
+    for (size_t k = 0; k < Ks; ++k) t_d.push_back(d->sched[k].t);
+    const int strip = scene_fir_sched_strip(n, m.N);
+    std::vector<FirSegment> segs;
+    std::vector<FirStrip> strips;
+    fir_segments(t, n, (int)S, t_f.data(), f.have_to, f.have_from, f.t_set, segs);
+    fir_strips(segs, t, f.R, strip, strips);
+    bool any_from = false;
+    for (const FirStrip &e : strips) any_from = any_from || e.set_from >= 0;
+    // one staged block: filter times | delay times | strips | onsets [S][N] | delays [K_d][N] | taps [S][C][N][K]
+    const size_t cn = (size_t)m.C * m.N, nt = m.taps_floats(), set_floats = cn * m.LP;
+    const size_t off_td = S * sizeof(long long), off_strips = off_td + Kd * sizeof(long long),
+                 off_on = off_strips + strips.size() * sizeof(FirStrip), off_dl = off_on + S * m.N * sizeof(int),
+                 off_taps = off_dl + Kd * m.N * sizeof(float), set_bytes = off_taps + S * nt * sizeof(float);
+    char *h_sets = nullptr;
+    GROWTRY(grow(m.d_sets, set_bytes, stream_), "scene_fir: cannot allocate the step's scheduled sets", "scene_fir: scheduled sets");
+    GROWTRY(grow(m.d_pool, (S + 2) * set_floats, stream_), "scene_fir: cannot allocate the step's pool of filter sets", "scene_fir: filter pool");
+    GROWTRY(grow(m.d_onpool, (S + 2) * (size_t)m.N, stream_), "scene_fir: cannot allocate the step's pool of filter sets", "scene_fir: onset pool");
+    if (d) GROWTRY(grow(d->d_rec, (Kd + 1) * d->p.size(), stream_), "scene_fir: cannot allocate the step's delay records", "scene_fir: delay records");
+    GROWTRY(m.stage.acquire(set_bytes, h_sets), "scene_fir: cannot allocate the staging of the step's scheduled sets", "scene_fir: staging");
+    float *out;
+    GROWTRY(m.out.resolve(d_out, (size_t)m.C * n, stream_, out), "scene_fir: cannot allocate the output", "scene_fir: output");
+    GROWTRY(grow(m.parts, (size_t)2 * m.C * groups * n, stream_), "scene_fir: cannot allocate the partial rows", "scene_fir: partial rows");
+    if (d) HIPTRY(d->refresh());
+    // nothing refuses from here on
+    std::memcpy(h_sets, t_f.data(), S * sizeof(long long));
+    std::memcpy(h_sets + off_td, t_d.data(), Kd * sizeof(long long));
+    std::memcpy(h_sets + off_strips, strips.data(), strips.size() * sizeof(FirStrip));
+    std::vector<const std::vector<int> *> onsets;        // of the step's sets, in order
+    {
+        size_t k = 0;
+        if (f.pending) {
+            std::memcpy(h_sets + off_taps, m.pend_taps.data(), nt * sizeof(float));
+            onsets.push_back(&m.pend_onset);
+            ++k;
+        }
+        for (size_t i = 0; i < Ss; ++i, ++k) {
+            std::memcpy(h_sets + off_taps + k * nt * sizeof(float), m.sched[i].taps.data(), nt * sizeof(float));
+            onsets.push_back(&m.sched[i].onset);
+        }
+        for (k = 0; k < S; ++k) std::memcpy(h_sets + off_on + k * m.N * sizeof(int), onsets[k]->data(), (size_t)m.N * sizeof(int));
+        k = 0;
+        if (d && d->have_pend) std::memcpy(h_sets + off_dl + (k++) * m.N * sizeof(float), d->pend.data(), (size_t)m.N * sizeof(float));
+        for (size_t i = 0; i < Ks; ++i, ++k) std::memcpy(h_sets + off_dl + k * m.N * sizeof(float), d->sched[i].v.data(), (size_t)m.N * sizeof(float));
+    }
+    HIPTRY(hipMemcpyAsync(m.d_sets, h_sets, set_bytes, hipMemcpyHostToDevice, stream_));
+    HIPTRY(m.stage.record(stream_));
+    // the pool: 0 / 1 the sets the step begins with, 2 + k its own, prepared in one launch
+    const int to = f.to_idx, from = to ^ 1;
+    const size_t on_bytes = (size_t)m.N * sizeof(int);
+    if (f.have_to) {
+        HIPTRY(hipMemcpyAsync(m.d_pool, m.d_P[to], set_floats * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+        HIPTRY(hipMemcpyAsync(m.d_onpool, m.d_onset[to], on_bytes, hipMemcpyDeviceToDevice, stream_));
+    }
+    if (f.have_to && f.fading(t)) {
+        HIPTRY(hipMemcpyAsync(m.d_pool.p + set_floats, m.d_P[from], set_floats * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+        HIPTRY(hipMemcpyAsync(m.d_onpool.p + m.N, m.d_onset[from], on_bytes, hipMemcpyDeviceToDevice, stream_));
+    }
+    if (S) {
+        HIPTRY(hipMemcpyAsync(m.d_onpool.p + 2 * (size_t)m.N, m.d_sets.p + off_on, S * on_bytes, hipMemcpyDeviceToDevice, stream_));
+        const int prc = launch_scene_fir_prepare((const float *)(m.d_sets.p + off_taps), (long long)(S * cn), m.K, m.d_pool.p + 2 * set_floats, stream_);
+        if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_prepare");
+    }
+    if (d && d->dirty) {
+        char *h_p;
+        HIPTRY(d->up.acquire(h_p));
+        const size_t bytes = d->p.size() * sizeof(SceneParam);
+        std::memcpy(h_p, d->p.data(), bytes);
+        HIPTRY(hipMemcpyAsync(d->d_p, h_p, bytes, hipMemcpyHostToDevice, stream_));
+        HIPTRY(d->up.record(stream_));
+        d->dirty = false;
+    }
+    FirSchedStep a{};
+    a.rows = last_audio_; a.n_obj = m.N; a.n = n;
+    a.hist = m.hist.cur(); a.hist_next = m.hist.next(); a.H = m.H;
+    if (d) {
+        a.hist_x = d->hist_x.cur(); a.hist_x_next = d->hist_x.next(); a.Hx = d->Hx;
+        a.params = d->d_p; a.rec = d->d_rec; a.t_d = (const long long *)(m.d_sets.p + off_td);
+        a.targets = (const float *)(m.d_sets.p + off_dl); a.Kd = (int)Kd; a.Rd = d->ramp; a.any_set = d->any_set ? 1 : 0;
+    }
+    a.pool = m.d_pool; a.onpool = m.d_onpool; a.t_f = (const long long *)m.d_sets.p; a.S = (int)S;
+    a.have_to0 = f.have_to ? 1 : 0; a.have_from0 = f.have_from ? 1 : 0; a.t_set0 = f.t_set;
+    a.strips = (const FirStrip *)(m.d_sets.p + off_strips); a.n_strips = (int)strips.size(); a.strip = strip; a.any_from = any_from ? 1 : 0;
+    a.C = m.C; a.K = m.K; a.R = f.R; a.t0 = t;
+    a.parts = m.parts; a.out = out;
+    const int lrc = launch_scene_fir_sched(a, stream_);
+    if (lrc != 0) return hip_fail((hipError_t)lrc, "launch_scene_fir_sched");
+    if (S) {
+        // what S plain sets between cut steps would have left: the last set in slot 0, in force; the one before it in slot 1
+        const size_t i_to = S + 1, i_from = S >= 2 ? S : 0;
+        const bool have_from = S >= 2 || f.have_to;
+        HIPTRY(hipMemcpyAsync(m.d_P[0], m.d_pool.p + i_to * set_floats, set_floats * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+        HIPTRY(hipMemcpyAsync(m.d_onset[0], m.d_onpool.p + i_to * m.N, on_bytes, hipMemcpyDeviceToDevice, stream_));
+        if (have_from) {
+            HIPTRY(hipMemcpyAsync(m.d_P[1], m.d_pool.p + i_from * set_floats, set_floats * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+            HIPTRY(hipMemcpyAsync(m.d_onset[1], m.d_onpool.p + i_from * m.N, on_bytes, hipMemcpyDeviceToDevice, stream_));
+        }
+        const std::vector<int> on_to = *onsets[S - 1];
+        m.onset_from = S >= 2 ? *onsets[S - 2] : m.onset_to;
+        m.onset_to = on_to;
+        f.to_idx = 0;
+        f.have_from = have_from;
+        f.have_to = true;
+        f.t_set = t_f[S - 1];
+        f.pending = false;
+        m.sched.erase(m.sched.begin(), m.sched.begin() + (long)Ss);
+    }
+    if (d && Kd) {
+        // d_p is now the block of the last set; the host's copy follows behind the mix, and is taken over by who next needs it
+        HIPTRY(hipMemcpyAsync(d->p_back, d->d_p, d->p.size() * sizeof(SceneParam), hipMemcpyDeviceToHost, stream_));
+        HIPTRY(hipEventRecord(d->ev_back, stream_));
+        d->p_stale = true;
+        d->ramping = (d->any_set || Kd > 1) && d->ramp > 0;
+        d->t_set = t_d[Kd - 1];
+        d->any_set = true;
+        d->have_pend = false;
+        d->sched.erase(d->sched.begin(), d->sched.begin() + (long)Ks);
+    }
+    if (d) d->hist_x.flip();
+    m.hist.flip();
+    m.clock.advance(n, tot_steps_);
+    ++m.n_mixes;
+    m.out.wrote(out, last_nb_);
     return PBSO_OK;
 }
 

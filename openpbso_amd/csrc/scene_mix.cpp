@@ -14,49 +14,6 @@ namespace pbso {
 // a scheduled set that is not in force yet: its targets in f32 as given, the gains [C][N], then the delays where it has any
 struct PendingSet { long long t; bool has_delay; std::vector<float> v; };
 
-// Pinned staging of one step's scheduled sets, in a ring as UploadRing, but each slot grows to what a step needs.  A slot is
-// rewritten (or freed for a larger one) only once the copy that last read it is done.
-struct StagingRing {
-    static constexpr int SLOTS = UploadRing::UP_SLOTS;
-    char *block[SLOTS] = {};
-    size_t cap[SLOTS] = {};
-    hipEvent_t ev[SLOTS] = {};
-    bool used[SLOTS] = {};
-    int slot = 0;
-    StagingRing() = default;
-    StagingRing(const StagingRing &) = delete;
-    StagingRing &operator=(const StagingRing &) = delete;
-    ~StagingRing() {
-        for (int i = 0; i < SLOTS; ++i) {
-            if (block[i]) (void)hipHostFree(block[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    }
-    // the next slot's block, at least `bytes` long, once its last copy has left it
-    hipError_t acquire(size_t bytes, char *&b) {
-        hipError_t e = hipSuccess;
-        if (!ev[slot] && (e = hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming)) != hipSuccess) { ev[slot] = nullptr; return e; }
-        if (used[slot] && (e = hipEventSynchronize(ev[slot])) != hipSuccess) return e;
-        used[slot] = false;
-        if (cap[slot] < bytes) {
-            if (block[slot]) (void)hipHostFree(block[slot]);
-            block[slot] = nullptr;
-            cap[slot] = 0;
-            if ((e = hipHostMalloc((void **)&block[slot], bytes, hipHostMallocDefault)) != hipSuccess) { block[slot] = nullptr; return e; }
-            cap[slot] = bytes;
-        }
-        b = block[slot];
-        return hipSuccess;
-    }
-    hipError_t record(hipStream_t s) {
-        const hipError_t e = hipEventRecord(ev[slot], s);
-        if (e != hipSuccess) return e;
-        used[slot] = true;
-        slot = (slot + 1) % SLOTS;
-        return hipSuccess;
-    }
-};
-
 struct SceneMix {
     int C = 0, N = 0, max_delay = 0, ramp = 0, H = 0;   // H = max_delay + 1 samples of history per object
     std::vector<SceneParam> p;                           // [C][N][2] (gain, delay): the host's copy, uploaded when it changed

@@ -208,6 +208,53 @@ class Group:
         assert d.size == len(self._modes)
         self._chk(self._l.pbso_group_scene_fir_set_delay(self._h, d.ctypes.data_as(C.POINTER(C.c_float))))
 
+    def scene_fir_set_at(self, t_set, taps, onset=None):
+        """pbso_group_scene_fir_set_at: as scene_fir_set, taking effect at the absolute sample t_set"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        c = getattr(self, "_fir_c", 0)                               # (not enabled yet: the call itself says so)
+        assert not c or (h.size == c * len(self._modes) * self._fir_k and (d is None or d.size == len(self._modes)))
+        self._chk(self._l.pbso_group_scene_fir_set_at(self._h, int(t_set), h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def scene_fir_schedule(self, t_set, taps, onset=None):
+        """pbso_group_scene_fir_schedule: t_set [n_sets], taps [n_sets][n_channels][n_objects of the job][n_taps], onset
+        [n_sets][n_objects of the job] by global id"""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        c = getattr(self, "_fir_c", 0)
+        assert not c or (h.size == t.size * c * len(self._modes) * self._fir_k and (d is None or d.size == t.size * len(self._modes)))
+        self._chk(self._l.pbso_group_scene_fir_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def scene_fir_set_delay_at(self, t_set, delay):
+        """pbso_group_scene_fir_set_delay_at: as scene_fir_set_delay, taking effect at the absolute sample t_set"""
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == len(self._modes)
+        self._chk(self._l.pbso_group_scene_fir_set_delay_at(self._h, int(t_set), d.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_delay_schedule(self, t_set, delay):
+        """pbso_group_scene_fir_delay_schedule: t_set [n_sets], delay [n_sets][n_objects of the job] by global id"""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == t.size * len(self._modes)
+        self._chk(self._l.pbso_group_scene_fir_delay_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                              d.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_clear_schedule(self):
+        """pbso_group_scene_fir_clear_schedule: drops the scheduled filter and delay sets not yet in force on every local rank"""
+        self._chk(self._l.pbso_group_scene_fir_clear_schedule(self._h))
+
+    def scene_fir_schedule_info(self):
+        """pbso_scene_fir_schedule_info of the first local rank that has objects (the ranks are mixed in lockstep and agree)"""
+        for rank in self.local_ranks():
+            lo, hi = self.span(rank)
+            if hi > lo:
+                return self.engine(rank).scene_fir_schedule_info()
+        raise PbsoError(capi.ERR_STATE, "scene_fir_schedule_info: no local rank has objects")
+
     def sync(self):
         self._chk(self._l.pbso_group_sync(self._h))
 

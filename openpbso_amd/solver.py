@@ -702,6 +702,52 @@ class Engine:
         self._chk(self._l.pbso_scene_fir_delay_info(self._h, v))
         return {"max_delay": v[0], "ramp_samples": v[1], "ramp_end": v[2], "sets": v[3]}
 
+    # ... and the schedule of both kinds of set: sets that take effect at absolute samples, any number of them inside one step
+    def scene_fir_set_at(self, t_set, taps, onset=None):
+        """pbso_scene_fir_set_at: as scene_fir_set, taking effect at the absolute sample t_set (inside a step or not)"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        c = getattr(self, "_fir_c", 0)                               # (not enabled yet: the call itself says so)
+        assert not c or (h.size == c * len(self.n_modes) * self._fir_k and (d is None or d.size == len(self.n_modes)))
+        self._chk(self._l.pbso_scene_fir_set_at(self._h, int(t_set), h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def scene_fir_schedule(self, t_set, taps, onset=None):
+        """pbso_scene_fir_schedule: t_set [n_sets] ascending absolute samples, taps [n_sets][n_channels][n_objects][n_taps], onset
+        [n_sets][n_objects] ints; onset None keeps the onsets in all of them.  All or nothing."""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        c = getattr(self, "_fir_c", 0)
+        assert not c or (h.size == t.size * c * len(self.n_modes) * self._fir_k and (d is None or d.size == t.size * len(self.n_modes)))
+        self._chk(self._l.pbso_scene_fir_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)), h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def scene_fir_set_delay_at(self, t_set, delay):
+        """pbso_scene_fir_set_delay_at: as scene_fir_set_delay, taking effect at the absolute sample t_set"""
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == len(self.n_modes)
+        self._chk(self._l.pbso_scene_fir_set_delay_at(self._h, int(t_set), d.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_delay_schedule(self, t_set, delay):
+        """pbso_scene_fir_delay_schedule: t_set [n_sets] ascending absolute samples, delay [n_sets][n_objects].  All or nothing."""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        d = np.ascontiguousarray(delay, dtype=np.float32)
+        assert d.size == t.size * len(self.n_modes)
+        self._chk(self._l.pbso_scene_fir_delay_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        d.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_clear_schedule(self):
+        """pbso_scene_fir_clear_schedule: drops the scheduled filter and delay sets not yet in force"""
+        self._chk(self._l.pbso_scene_fir_clear_schedule(self._h))
+
+    def scene_fir_schedule_info(self):
+        """pbso_scene_fir_schedule_info: t of the next mixed sample, filter sets pending, delay sets pending, the smallest t_set the
+        next scheduled filter set may have"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_fir_schedule_info(self._h, v))
+        return {"t": v[0], "pending": v[1], "pending_delay": v[2], "next_t_min": v[3]}
+
     # -- scene reverb: n_in device-resident bus signals through K taps per (output channel, input), history kept across steps ----
     def scene_reverb_enable(self, n_in, n_out, n_taps, xfade_samples=0):
         """pbso_scene_reverb_enable: from the next step on, every step is processed exactly once (scene_reverb)"""

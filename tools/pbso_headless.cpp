@@ -46,6 +46,10 @@
 //                    <delay in samples> set copy's fractional delay in front of its filters from that buffer on, ramped over N
 //                    samples (default 441; a moving source's Doppler shift).  max_delay is the file's largest value, rounded
 //                    up; the run is cut at these lines' buffers too.
+//   --fir-schedule   with --fir (and --fir-delay when given): all lines are scheduled up front at sample <buffer> * frames
+//                    (pbso_scene_fir_set_at / _set_delay_at; with --devices the group's calls) and no longer cut the run -- the
+//                    same samples in the WAV (byte for byte with --time-chunks 1 on both commands), in one step unless another
+//                    script (--retune) cuts it
 //   --reverb FILE [--reverb-xfade N]     with --channels C and one of --pan / --fir: the room behind the mix (pbso_scene_reverb).  The
 //                    file is an impulse response per output channel, raw little-endian float32 [C][K], K = file size / 4 C up to
 //                    131072; the send bus is the object mix (pbso_mix_objects, one input), and the WAV is dry + wet: every
@@ -229,6 +233,7 @@ struct Scene {
     bool pan_schedule = false;                           // --pan-schedule: the lines are scheduled up front and cut nothing
     // --fir: the scene filter mix's script instead of the pan script
     bool fir = false;
+    bool fir_schedule = false;                           // --fir-schedule: the --fir and --fir-delay lines are scheduled up front and cut nothing
     int xfade = 441, n_taps = 0, max_onset = 0;
     std::vector<FirLine> fir_lines;
     std::vector<std::vector<float>> fir_files;           // [C][K] each
@@ -244,9 +249,9 @@ struct Scene {
         for (const Pan &p : lines)
             if (!pan_schedule && p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         for (const FirLine &p : fir_lines)
-            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+            if (!fir_schedule && p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         for (const FirDelayLine &p : fir_delay_lines)
-            if (p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
+            if (!fir_schedule && p.b > 0 && p.b < n_buffers) c.push_back((int)p.b);
         std::sort(c.begin(), c.end());
         c.erase(std::unique(c.begin(), c.end()), c.end());
         return c;
@@ -295,6 +300,22 @@ struct Scene {
                 any = true;
             }
         return any;
+    }
+    // --fir-schedule: every buffer that has --fir lines, in order, as one set at its first sample: set(t_set, taps, onset); and the
+    // same for the --fir-delay lines: set_delay(t_set, delay)
+    template <class Set, class SetDelay>
+    void schedule_fir(std::vector<float> &taps, std::vector<int> &onset, std::vector<float> &delay, Set set, SetDelay set_delay) const {
+        std::vector<long> at, at_delay;
+        for (const FirLine &p : fir_lines) at.push_back(p.b);
+        for (const FirDelayLine &p : fir_delay_lines) at_delay.push_back(p.b);
+        for (std::vector<long> *v : {&at, &at_delay}) {
+            std::sort(v->begin(), v->end());
+            v->erase(std::unique(v->begin(), v->end()), v->end());
+        }
+        for (long b : at)
+            if (fir_set_at(b, taps, onset)) set((int64_t)b * PBSO_FRAMES_PER_BUFFER, taps.data(), onset.data());
+        for (long b : at_delay)
+            if (fir_delay_set_at(b, delay)) set_delay((int64_t)b * PBSO_FRAMES_PER_BUFFER, delay.data());
     }
 };
 
@@ -463,10 +484,16 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             scene->schedule_pan(gain, delay, [&](int64_t t, const float *gn, const float *dl) {
                 gcheck(g, pbso_group_scene_mix_set_at(g, t, gn, dl), "group_scene_mix_set_at");
             });
+        if (scene->fir_schedule)
+            scene->schedule_fir(taps, onset, fir_delay,
+                                [&](int64_t t, const float *h, const int *on) { gcheck(g, pbso_group_scene_fir_set_at(g, t, h, on), "group_scene_fir_set_at"); },
+                                [&](int64_t t, const float *dl) { gcheck(g, pbso_group_scene_fir_set_delay_at(g, t, dl), "group_scene_fir_set_delay_at"); });
         const std::vector<int> cuts = retune.cut(scene->cuts(n_buffers), n_buffers);
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
             retune.apply_at(cuts[k], group_set);
-            if (scene->fir) {
+            if (scene->fir_schedule) {
+                // (scheduled up front)
+            } else if (scene->fir) {
                 if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
                 if (scene->fir_delay_set_at(cuts[k], fir_delay)) gcheck(g, pbso_group_scene_fir_set_delay(g, fir_delay.data()), "group_scene_fir_set_delay");
             } else if (scene->pan_schedule) {
@@ -547,6 +574,7 @@ int main(int argc, char **argv) {
         else if (a == "--channels") scene.channels = std::atoi(val().c_str());
         else if (a == "--pan") pan = val();
         else if (a == "--pan-schedule") scene.pan_schedule = true;
+        else if (a == "--fir-schedule") scene.fir_schedule = true;
         else if (a == "--time-chunks") time_chunks = std::atoi(val().c_str());
         else if (a == "--retune") retune_arg = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
@@ -760,6 +788,7 @@ int main(int argc, char **argv) {
     const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
     if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
     if (scene.pan_schedule && pan.empty()) die("--pan-schedule needs --pan FILE: it schedules that script's lines");
+    if (scene.fir_schedule && fir.empty()) die("--fir-schedule needs --fir FILE: it schedules that script's lines (and --fir-delay's)");
     if (!fir_delay.empty() && fir.empty()) die("--fir-delay needs --fir FILE: the delay sits in front of the filter mix");
     if (mixed && (scene.channels < 1 || scene.channels > 8)) die("--channels must be 1 .. 8");
     if (!fir.empty()) {
@@ -976,12 +1005,18 @@ int main(int argc, char **argv) {
                 scene.schedule_pan(gain, delay, [&](int64_t t, const float *gn, const float *dl) {
                     check(e, pbso_scene_mix_set_at(e, t, gn, dl), "scene_mix_set_at");
                 });
+            if (scene.fir_schedule)
+                scene.schedule_fir(taps, onset, delay_now,
+                                   [&](int64_t t, const float *h, const int *on) { check(e, pbso_scene_fir_set_at(e, t, h, on), "scene_fir_set_at"); },
+                                   [&](int64_t t, const float *dl) { check(e, pbso_scene_fir_set_delay_at(e, t, dl), "scene_fir_set_delay_at"); });
             std::vector<int> cuts = retune.cut(scene.cuts(n_buffers), n_buffers);
             if (n_tail) cuts.push_back(n_run);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
                 if (cuts[k] < n_buffers) retune.apply_at(cuts[k], engine_set);
                 if (cuts[k] >= n_buffers) {
                     // (--limit's tail: the script ended with the run)
+                } else if (scene.fir_schedule) {
+                    // (scheduled up front)
                 } else if (scene.fir) {
                     if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
                     if (scene.fir_delay_set_at(cuts[k], delay_now)) check(e, pbso_scene_fir_set_delay(e, delay_now.data()), "scene_fir_set_delay");
