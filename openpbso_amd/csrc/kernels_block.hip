@@ -460,7 +460,10 @@ __global__ __launch_bounds__(MAXT) void iir_block_kernel(
     };
     // The vector burst as ONE asm statement (round 6; builds without DUMP): the step on the (Q, D) register PAIR as two v_pk_fma_f32,
     //     t = (P11 - 1, P21) * (Q, Q) + (Q, D);    x' = (P12, P22 - 1) * (D, D) + t
-    // (the same map: D' = P21 Q + D + (P22 - 1) D; P22 - 1 is exact in f32 for P22 in [0.5, 2]).  Every operand is a 64-bit pair, so
+    // (the same map: D' = P21 Q + D + (P22 - 1) D.  P22 - 1 is formed in f32 from the rounded P22: exact only for P22 in [0.5, 2], and
+    // a 16-sample coarse step's P22 is not confined to that range -- elsewhere the coefficient is rounded a second time, unlike P11 - 1,
+    // which the host rounds once from double.  The DUMP builds keep the four-instruction step_p: tests/test_gpu_listener_mix_shapes.py
+    // bounds the difference between the two, DESIGN.md section 2 has the figure).  Every operand is a 64-bit pair, so
     // the sixteen steps and their eight ds_write2_b64 fit one statement: no s_nop between statements (the compiler puts one behind
     // every inline-asm definition that the next statement reads: 32 per burst), half the instructions to issue, the stores between the
     // steps.  scripts/microbench/gen_burst_shapes.py, beside a partner wave and the b128 matrix burst: 1264 cycles per slice against

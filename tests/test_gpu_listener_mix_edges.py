@@ -5,30 +5,9 @@ import numpy as np
 import pytest
 
 from openpbso_amd import ForceMessage, capi, synth
+from tests.listener_mix_ref import oracle_per_listener as _oracle_per_listener
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_per_listener(lam, omaps, pos, nb, hits, clear_at=()):
-    from oracle import oracle_py as orc
-    out = []
-    for p in pos:
-        s = orc.Solver(lam, synth.RHO, synth.ALPHA, synth.BETA)
-        if omaps is not None:
-            s.read_ffat_maps(omaps)
-            s.compute_transfer(p)
-        else:
-            s.set_use_transfer(False)
-        bufs = []
-        for b in range(nb):
-            if b in clear_at:
-                s.enqueue_force(None, clear_all=True)
-            elif b in hits:
-                s.enqueue_force(hits[b])
-            snd = s.step()
-            bufs.append(np.zeros(513) if snd is None or snd[0] is None else snd[0])
-        out.append(np.concatenate(bufs))
-    return np.array(out)
 
 
 @pytest.mark.parametrize("form", [capi.FORM_BLOCK, capi.FORM_BLOCK_BF16])
