@@ -3,17 +3,38 @@
 // v_mfma_f32_16x16x4_f32 (kernels_fir.hip has the formulation) from a window of samples in padded LDS, and both end in the same
 // second stage.
 //
-// The first stages' bodies -- staging the window and the tap rows, the walk over window positions, the write-out of the
-// accumulators -- are the same text in both kernels and are NOT here: each of these pieces, moved into a forced-inline function
-// on its own, changed the instruction stream of every scene_fir_stage1<C> (the compiler optimises an inline function before it
-// inlines it, and the schedule that comes out differs), and these kernels stay instruction for instruction what was measured.
-// What is here compiles to the same instructions as when every file spelled it out.
+// The first stages stay instruction for instruction what was measured, and that decides how their bodies -- staging the window
+// and the tap rows, the walk over window positions, the write-out of the accumulators -- can be shared.  A piece moved into a
+// forced-inline function on its own, or a whole body called from thin __global__ wrappers, changes the instruction stream (the
+// compiler optimises an inline function before it inlines it, and the schedule that comes out differs); so does a kernel whose
+// argument layout moves.  ONE kernel template whose variant parts are `if constexpr` regions, each variant with the kernel
+// arguments it was measured with, does not: that is how the variants of scene_fir_stage1 (kernels_fir.hip) share their body.
+// scene_reverb_stage1 has another loop structure (one window, the taps in pieces): what it has in common with them are pieces
+// of a body, so it spells them out itself.  What is here compiles to the same instructions as when every file spelled it out.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace pbso {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// f(std::integral_constant<int, C>{}) for a channel count the caller has checked (1 .. 8 = SCENE_MAX_CHANNELS): the switch from
+// a launch's C to the kernels built per channel count
+template <class F>
+void for_channel_count(int C, F &&f) {
+    switch (C) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
 
 // window position i of a strip in LDS: one pad word per 16, so that the 16 blocks a B operand reads at one m lie in 16 banks
 __device__ __forceinline__ int win_at(int i) { return i + (i >> 4); }

@@ -274,12 +274,12 @@ public:
     int read_scene_fir(float *out, size_t n);
     int scene_fir_reset();
     int scene_fir_info(int64_t out[4]);
-    // ... behind a ramped fractional delay per object (kernels_fir_delay.hip)
+    // ... behind a ramped fractional delay per object
     int scene_fir_delay_enable(int max_delay, int ramp_samples);
     int scene_fir_set_delay(const float *delay);
     int scene_fir_delay_info(int64_t out[4]);
-    // ... and the schedule of both kinds of set: sets that take effect at absolute samples given by the caller (kernels_fir_sched.hip;
-    // `call`: the entry point, for the messages)
+    // ... and the schedule of both kinds of set: sets that take effect at absolute samples given by the caller
+    // (`call`: the entry point, for the messages)
     int scene_fir_schedule(const char *call, int n_sets, const int64_t *t_set, const float *taps, const int *onset);
     int scene_fir_delay_schedule(const char *call, int n_sets, const int64_t *t_set, const float *delay);
     int scene_fir_clear_schedule();

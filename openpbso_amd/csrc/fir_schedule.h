@@ -1,6 +1,6 @@
 // The integer arithmetic of the scene filter mix's schedule (include/openpbso_amd.h "scene filter mix", SCHEDULE): when a
 // scheduled filter set may take effect, and how a step with filter sets inside it is cut into the work strips that
-// scene_fir_sched_stage1 (kernels_fir_sched.hip) runs.  Integers only and no HIP call: scene_fir.cpp builds a step's table with it,
+// the scheduled scene_fir_stage1 (kernels_fir.hip) runs.  Integers only and no HIP call: scene_fir.cpp builds a step's table with it,
 // the kernels read the entries, and tests/cpp/fir_schedule_check.cpp pins all of it against a per-sample labelling on the host
 // compiler alone.
 #pragma once

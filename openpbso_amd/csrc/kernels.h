@@ -382,7 +382,7 @@ int launch_scene_fir_prepare(const float *taps, long long n_co, int K, float *P,
 int launch_scene_fir(const float *rows, int n_obj, long long n, const float *hist, float *hist_next, int H, const float *P_to,
                      const float *P_from, const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0,
                      long long t_set, int R, float *parts, float *out, hipStream_t stream);
-// pbso_scene_fir behind pbso_scene_fir_delay_enable (kernels_fir_delay.hip): the same with z_o in place of x_o, z_o(t0 + j) = the
+// pbso_scene_fir behind pbso_scene_fir_delay_enable (kernels_fir.hip): the same with z_o in place of x_o, z_o(t0 + j) = the
 // scene mix's read of hist_x ++ rows at t0 + j - d_o(t0 + j), d_o = ramp_value(params[o], ., Rd); params [n_obj].  hist_z [n_obj][H]
 // the H samples of z before the step, hist_x [n_obj][Hx] the Hx = max_delay + 1 samples of x before it.  Then hist_z_next = the
 // last H samples of hist_z ++ z(step) and hist_x_next = the last Hx samples of hist_x ++ rows.
@@ -391,7 +391,7 @@ int launch_scene_fir_delay(const float *rows, int n_obj, long long n, const floa
                            const int *onset_to, const int *onset_from, int C, int K, long long n_fade, long long t0, long long t_set, int R,
                            float *parts, float *out, hipStream_t stream);
 
-// The same step with scheduled sets taking effect inside it (pbso_scene_fir_schedule / _delay_schedule; kernels_fir_sched.hip).
+// The same step with scheduled sets taking effect inside it (pbso_scene_fir_schedule / _delay_schedule; kernels_fir.hip).
 // The step's filter sets lie in a pool: [S + 2] sets of padded reversed taps [C][n_obj][LP] with onsets [S + 2][n_obj], 0 / 1 the
 // set in force / faded out when the step begins (have_to0 / have_from0, since t_set0), 2 + k the set that takes effect at the
 // ascending absolute sample t_f[k] in [t0, t0 + n).  strips: the step's work strips (fir_schedule.h) of at most `strip` samples,

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_mfma.h"
+#include "delay_read.h"
 #include "kernels.h"
 
 namespace pbso {
@@ -18,12 +19,7 @@ namespace pbso {
 namespace {
 constexpr int SCENE_GROUP = 32;                          // = MIX_GROUP of kernels_exact.hip (mix_objects_groups)
 
-// the read position t - d as i0 + f with i0 = t - off: a fraction of exactly 0 reads x(i0) itself
-__device__ __forceinline__ void delay_split(double d, long long *off, float *f) {
-    const double fl = floor(d), fr = d - fl;             // (exact)
-    *off = (long long)fl + (fr != 0.0 ? 1 : 0);
-    *f = fr != 0.0 ? (float)(1.0 - fr) : 0.f;
-}
+// (delay_split and interp: delay_read.h)
 // x_o at the step's local sample j: the step's row for j >= 0, the history before it for -H <= j < 0.  Every read of the mix
 // lies there (0 <= d <= max_delay = H - 1, and x(i0 + 1) is read only with a fraction, i0 + 1 <= t); the clamp keeps an address
 // in the buffers whatever the arguments.
@@ -31,7 +27,6 @@ __device__ __forceinline__ float fetch(const float *__restrict__ row, const floa
     j = j < -(long long)H ? -(long long)H : (j >= n ? n - 1 : j);
     return j >= 0 ? row[j] : hrow[H + j];
 }
-__device__ __forceinline__ float interp(float x0, float x1, float f) { return f == 0.f ? x0 : x0 + f * (x1 - x0); }
 }  // namespace
 
 // One wave per (64 samples, group of 32 objects), one sample per lane: every load of the wave reads 64 consecutive floats of one

@@ -47,8 +47,8 @@ __global__ __launch_bounds__(256) void reverb_prepare_kernel(const float *__rest
 // LDS once; the C tap rows of the segment follow in pieces of RV_PIECE window positions.  Every wave walks the positions four at a
 // time: one A operand per channel (the taps), one B operand per tile (the window), C T MFMAs on C T accumulators.
 //   LDS: win [win_at(W) + 1] | taps [C][RV_TPW],  W = strip + Mp window positions
-// (The lane decomposition, the batched staging, the two-round walk and the write-out below are the same text in
-//  scene_fir_stage1 of kernels_fir.hip -- conv_mfma.h says why they are not shared: an edit here wants the same edit there.)
+// (The lane decomposition, the batched staging, the two-round walk and the write-out below are those of scene_fir_stage1 of
+//  kernels_fir.hip in another loop structure: conv_mfma.h says why pieces of a body are not shared.)
 template <int C, int T>
 __global__ __launch_bounds__(256) void scene_reverb_stage1(const float *__restrict__ in, int n_in, long long n, const float *__restrict__ hist,
                                                            int H, const float *__restrict__ P0, const float *__restrict__ P1, int K, int J,
@@ -214,15 +214,10 @@ int launch_scene_reverb(const float *in, int n_in, long long n, const float *his
         return (int)hipErrorInvalidValue;
     const int H = K - 1, rows = n_in * scene_reverb_segments(K);
     if (P_to) {
-        int rc;
-#define PBSO_REVERB_CASE(c) \
-    case c: rc = launch_stage1_c<c>(stream, in, n_in, n, hist, H, P_to, P_from, K, n_fade, parts); break;
-        switch (n_out) {
-            PBSO_REVERB_CASE(1) PBSO_REVERB_CASE(2) PBSO_REVERB_CASE(3) PBSO_REVERB_CASE(4) PBSO_REVERB_CASE(5) PBSO_REVERB_CASE(6)
-            PBSO_REVERB_CASE(7)
-        default: rc = launch_stage1_c<8>(stream, in, n_in, n, hist, H, P_to, P_from, K, n_fade, parts); break;
-        }
-#undef PBSO_REVERB_CASE
+        int rc = 0;
+        for_channel_count(n_out, [&](auto c) {
+            rc = launch_stage1_c<decltype(c)::value>(stream, in, n_in, n, hist, H, P_to, P_from, K, n_fade, parts);
+        });
         if (rc != 0) return rc;
     }
     // (nothing set yet: no rows, silence -- or add alone -- and the history moves on)

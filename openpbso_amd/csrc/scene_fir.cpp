@@ -3,11 +3,11 @@
 // the device, and the rule that every step is mixed exactly once.  It reads what a step left (last_audio_, last_nb_) and counts
 // steps by tot_steps_.  It knows bus_state.h, which holds what the buses have in common (the cross-fade's clock among it), and
 // nothing of the other buses.
-// The schedule (pbso_scene_fir_schedule, pbso_scene_fir_delay_schedule; kernels_fir_sched.hip): the filter and delay sets not yet in
+// The schedule (pbso_scene_fir_schedule, pbso_scene_fir_delay_schedule): the filter and delay sets not yet in
 // force wait on the host as given, each with its t_set; a mix takes those inside its step to the device in one staged block, cuts
 // the step into work strips (fir_schedule.h) and launches the schedule's kernels.  A step without a scheduled set inside it is
 // launched as it always was.
-// The optional delay stage (pbso_scene_fir_delay_enable; kernels_fir_delay.hip) puts the scene mix's ramped fractional delay per
+// The optional delay stage (pbso_scene_fir_delay_enable) puts the scene mix's ramped fractional delay per
 // object in front of the filters: its records, the second history (of x: `hist` then holds z), and the other launch.
 #include "bus_state.h"
 #include "fir_schedule.h"

@@ -9,7 +9,7 @@ sets computed).
                                                                   per call and the fraction of the flop floor
 
   python scripts/scene_fir_roofline.py --shape headline --delay steady|moving
-                                                                  the same behind the delay stage (kernels_fir_delay.hip): delays
+                                                                  the same behind the delay stage (the same file): delays
                                                                   set once (ramp 441, none running in a timed step: the
                                                                   steady path), or newly set before every step with a ramp
                                                                   longer than the step (every staged sample evaluates it)

@@ -1,5 +1,5 @@
 """The work-strip table and the validation arithmetic of the scene filter mix's schedule (csrc/fir_schedule.h: integers only, what
-scene_fir.cpp builds a step's launch from and the kernels of kernels_fir_sched.hip read) against a per-sample labelling of the step:
+scene_fir.cpp builds a step's launch from and the kernels of kernels_fir.hip read) against a per-sample labelling of the step:
 tests/cpp/fir_schedule_check.cpp is built with the host compiler and -fsanitize=address,undefined and run as a program of its own.
 No GPU, nothing loaded into Python."""
 import os

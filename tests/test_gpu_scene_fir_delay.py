@@ -1,4 +1,4 @@
-"""The delay stage of the scene filter mix (include/openpbso_amd.h "scene filter mix"; kernels_fir_delay.hip) on the device: a
+"""The delay stage of the scene filter mix (include/openpbso_amd.h "scene filter mix"; kernels_fir.hip) on the device: a
 ramped fractional delay per object in front of the K-tap filters.  Every comparison is BIT FOR BIT: with the undelayed mix where
 the two must agree, with the reference (tests/cpp/scene_fir_delay_ref.c and tests/cpp/scene_fir_ref.c through
 tests/scene_fir_delay_model.py, anchored by tests/test_scene_fir_delay_model.py) fed the rows Engine.audio() returned, and with

@@ -1,4 +1,4 @@
-"""The scene filter mix's schedule (include/openpbso_amd.h "scene filter mix", SCHEDULE; kernels_fir_sched.hip) on the device:
+"""The scene filter mix's schedule (include/openpbso_amd.h "scene filter mix", SCHEDULE; kernels_fir.hip) on the device:
 filter sets and delay sets that take effect at any sample of a step.  Every comparison is BIT FOR BIT, and never with the
 scheduled engine itself: the reference is the existing models (tests/scene_fir_model.py, tests/scene_fir_delay_model.py through
 tests/scene_fir_sched_ref.py) fed the rows Engine.audio() returned, cut at every t_set with a plain set before each piece; or a
