@@ -652,6 +652,43 @@ int pbso_scene_fir_set_delay_at(pbso_engine *e, int64_t t_set, const float *dela
 int pbso_scene_fir_delay_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const float *delay /* [n_sets][n_objects] */);
 int pbso_scene_fir_clear_schedule(pbso_engine *e);      /* drops the pending filter AND delay sets not yet in force */
 int pbso_scene_fir_schedule_info(pbso_engine *e, int64_t out[4]);
+/* The scene filter mix's BANK: the filters of a moving source come from a fixed measured table -- a head-related impulse response per
+ * direction, a handful of air-absorption filters, a set of wall reflections -- and what changes with time is which entries an
+ * object uses and with what weights.  The table is uploaded once and stays on the device; a set is then a few indices and weights
+ * per object instead of C * n_objects * K taps.
+ * A bank is F filters of [C][K] f32 taps, C and K those of the enabled mixer.  A bank set names, per object o, J entries
+ *   (index[o][j], weight[o][j]), 1 <= J <= 8, and optionally an onset per object as ever.  The taps it stands for are one chain per
+ *   (channel c, object o, tap k):
+ *       acc = 0.f;  for j = 0 .. J-1 ascending:  acc = fmaf(weight[o][j], bank[index[o][j]][c][k], acc);   h_co[k] = acc
+ *   (tests/cpp/scene_fir_bank_ref.c states it as plain C).  From there on a bank set IS the plain or scheduled set with those taps:
+ *   the same t_set rules and cross-fade, the same spacing rule t_set - t_prev + 1 >= R, onset == NULL meaning the onsets of the set
+ *   before it, the same counts in pbso_scene_fir_info and pbso_scene_fir_schedule_info, the same caps of 4096 filter sets per step
+ *   and of the pool.  The mixer's output is bit for bit what pbso_scene_fir_set / _set_at / _schedule gives for taps computed by
+ *   that chain on the host; J = 1 with weight 1.f is the bank's filter itself.  The same index may occur twice for one object;
+ *   weights may be 0 or negative.  The chain is evaluated on the device, straight into the padded reversed rows the filters read.
+ * Bank sets and taps sets are one ordered kind: they share the pending list and the spacing rule, a step may hold both, either may
+ *   follow the other, and pbso_scene_fir_set_bank -- a bank set waiting for the next mix -- follows the rules of pbso_scene_fir_set
+ *   (it replaces a plain set still waiting, of either form, and is replaced by one).
+ * VALIDATION, ALL OR NOTHING, before anything is taken.  Every index in [0, F), every weight finite, and per object
+ *   sum_j |weight[o][j]| * A <= FLT_MAX in fp64, A = max |bank tap| computed once at creation: every partial sum of the chain and
+ *   every resulting tap stay finite, without the taps being built on the host.  J outside 1 .. 8, a NULL index or weight, and what
+ *   the taps calls refuse (onset range, times) are PBSO_ERR_INVALID; a call before the enable or without a bank is PBSO_ERR_STATE.
+ * LIFETIME of the bank.  pbso_scene_fir_bank_create needs pbso_scene_fir_enable first; the taps must be finite, 1 <= F <= 1 << 20
+ *   (and n_objects * LP / 4 below 1 << 31).  If the bank cannot be allocated it returns PBSO_ERR_NOMEM and the mixer is as it was.
+ *   A second create replaces the bank; it is PBSO_ERR_STATE while bank sets are pending (scheduled, or waiting for the next mix).
+ *   Sets already taken by a mix are materialised taps and are not affected.  pbso_scene_fir_reset keeps the bank (and drops the
+ *   scheduled sets, bank sets among them, as ever).  A new pbso_scene_fir_enable drops the bank with everything else.
+ * pbso_scene_fir_bank_info: out[0] = F (0: no bank), out[1] = the largest J (8), out[2] = bank sets accepted since the enable
+ *   (they count in pbso_scene_fir_info out[3] as well), out[3] = device bytes of the bank.                                      */
+int pbso_scene_fir_bank_create(pbso_engine *e, int n_filters, const float *taps /* [F][C][K] */);
+int pbso_scene_fir_bank_info(pbso_engine *e, int64_t out[4]);
+int pbso_scene_fir_set_bank(pbso_engine *e, int J, const int *index /* [n_objects][J] */, const float *weight /* [n_objects][J] */,
+                            const int *onset /* [n_objects] or NULL = unchanged */);
+int pbso_scene_fir_set_bank_at(pbso_engine *e, int64_t t_set, int J, const int *index, const float *weight, const int *onset);
+int pbso_scene_fir_bank_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, int J,
+                                 const int *index    /* [n_sets][n_objects][J] */,
+                                 const float *weight /* [n_sets][n_objects][J] */,
+                                 const int *onset    /* [n_sets][n_objects], or NULL = unchanged by all of them */);
 
 /* Scene reverb: a bus effect behind the mixers -- n_in device-resident signals (a send bus: what pbso_mix_objects, pbso_scene_mix
  * or pbso_scene_fir just wrote, or some of their channels) convolved with a long impulse response per (output channel, input),
@@ -902,6 +939,17 @@ int pbso_group_scene_fir_schedule(pbso_group *g, int n_sets, const int64_t *t_se
 int pbso_group_scene_fir_set_delay_at(pbso_group *g, int64_t t_set, const float *delay);
 int pbso_group_scene_fir_delay_schedule(pbso_group *g, int n_sets, const int64_t *t_set, const float *delay);
 int pbso_group_scene_fir_clear_schedule(pbso_group *g);
+/* ... and the filter mix's bank: the whole bank on every local rank, rank by rank, as every enable of the group: should a rank
+ * after the first fail (PBSO_ERR_NOMEM), the ranks before it hold the new bank and the group counts itself as without a bank -- bank
+ * sets are PBSO_ERR_STATE -- until a pbso_group_scene_fir_bank_create succeeds on every rank.  index, weight
+ * [n_sets][n_objects of the whole job][J] and onset [n_sets][n_objects of the whole job] by global id: object-major, so every rank
+ * takes a contiguous slice (pbso_group_rank_span) of every set.  The values are checked for the whole job before any rank takes a
+ * set, the times and the state by the ranks' engines.                                                                          */
+int pbso_group_scene_fir_bank_create(pbso_group *g, int n_filters, const float *taps);
+int pbso_group_scene_fir_set_bank(pbso_group *g, int J, const int *index, const float *weight, const int *onset);
+int pbso_group_scene_fir_set_bank_at(pbso_group *g, int64_t t_set, int J, const int *index, const float *weight, const int *onset);
+int pbso_group_scene_fir_bank_schedule(pbso_group *g, int n_sets, const int64_t *t_set, int J, const int *index, const float *weight,
+                                       const int *onset);
 /* the last gather's result on a local rank, a device pointer: ALL -> [world_size * rows_per_rank][n_buffers * 513] (rank r's
  * objects from row r * rows_per_rank; shards smaller than the largest are padded with silent rows), ROOT -> the same on rank 0
  * and the rank's own rows elsewhere, MIX -> [n_buffers * 513], SCENE and FIR -> [C][n_buffers * 513].  rows / row_floats (may be NULL)

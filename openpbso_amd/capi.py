@@ -44,6 +44,10 @@ EXPORTS = [
     "pbso_scene_fir_clear_schedule", "pbso_scene_fir_schedule_info",
     "pbso_group_scene_fir_set_at", "pbso_group_scene_fir_schedule", "pbso_group_scene_fir_set_delay_at",
     "pbso_group_scene_fir_delay_schedule", "pbso_group_scene_fir_clear_schedule",
+    # ... and its bank (the filters stay on the device; a set is J (index, weight) pairs per object)
+    "pbso_scene_fir_bank_create", "pbso_scene_fir_bank_info", "pbso_scene_fir_set_bank", "pbso_scene_fir_set_bank_at",
+    "pbso_scene_fir_bank_schedule", "pbso_group_scene_fir_bank_create", "pbso_group_scene_fir_set_bank",
+    "pbso_group_scene_fir_set_bank_at", "pbso_group_scene_fir_bank_schedule",
     # the scene reverb (n_in bus signals through K taps, up to 1 << 17, per output channel and input)
     "pbso_scene_reverb_enable", "pbso_scene_reverb_set", "pbso_scene_reverb", "pbso_read_scene_reverb", "pbso_scene_reverb_reset",
     "pbso_scene_reverb_info",
@@ -269,6 +273,17 @@ def lib():
         l.pbso_group_scene_fir_set_delay_at.argtypes = [vp, C.c_int64, fp]
         l.pbso_group_scene_fir_delay_schedule.argtypes = [vp, C.c_int, tp, fp]
         l.pbso_group_scene_fir_clear_schedule.argtypes = [vp]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_fir_bank_create"):
+        tp = C.POINTER(C.c_int64)
+        l.pbso_scene_fir_bank_create.argtypes = [vp, C.c_int, fp]
+        l.pbso_scene_fir_bank_info.argtypes = [vp, tp]
+        l.pbso_scene_fir_set_bank.argtypes = [vp, C.c_int, ip, fp, ip]
+        l.pbso_scene_fir_set_bank_at.argtypes = [vp, C.c_int64, C.c_int, ip, fp, ip]
+        l.pbso_scene_fir_bank_schedule.argtypes = [vp, C.c_int, tp, C.c_int, ip, fp, ip]
+        l.pbso_group_scene_fir_bank_create.argtypes = [vp, C.c_int, fp]
+        l.pbso_group_scene_fir_set_bank.argtypes = [vp, C.c_int, ip, fp, ip]
+        l.pbso_group_scene_fir_set_bank_at.argtypes = [vp, C.c_int64, C.c_int, ip, fp, ip]
+        l.pbso_group_scene_fir_bank_schedule.argtypes = [vp, C.c_int, tp, C.c_int, ip, fp, ip]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_scene_reverb"):
         l.pbso_scene_reverb_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         l.pbso_scene_reverb_set.argtypes = [vp, fp]

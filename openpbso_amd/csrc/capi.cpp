@@ -624,6 +624,43 @@ int pbso_scene_fir_delay_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_scene_fir_bank_create(pbso_engine *e, int n_filters, const float *taps) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->scene_fir_bank_create(n_filters, taps);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_bank_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_bank_info(out);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_set_bank(pbso_engine *e, int J, const int *index, const float *weight, const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_bank_sets("scene_fir_set_bank", true, 1, nullptr, J, index, weight, onset);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_set_bank_at(pbso_engine *e, int64_t t_set, int J, const int *index, const float *weight, const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_bank_sets("scene_fir_set_bank_at", false, 1, &t_set, J, index, weight, onset);
+    GUARD_END(e)
+}
+
+int pbso_scene_fir_bank_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, int J, const int *index, const float *weight,
+                                 const int *onset) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->scene_fir_bank_sets("scene_fir_bank_schedule", false, n_sets, t_set, J, index, weight, onset);
+    GUARD_END(e)
+}
+
 int pbso_scene_reverb_enable(pbso_engine *e, int n_in, int n_out, int n_taps, int xfade_samples) {
     NEED(e);
     GUARD_BEGIN

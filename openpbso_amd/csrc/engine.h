@@ -284,6 +284,11 @@ public:
     int scene_fir_delay_schedule(const char *call, int n_sets, const int64_t *t_set, const float *delay);
     int scene_fir_clear_schedule();
     int scene_fir_schedule_info(int64_t out[4]);
+    // ... and the bank: F filters that stay on the device, and filter sets given as J (index, weight) pairs per object, plain
+    // (`plain`: n_sets is 1 and the set waits for the next mix) or scheduled
+    int scene_fir_bank_create(int n_filters, const float *taps);
+    int scene_fir_bank_info(int64_t out[4]);
+    int scene_fir_bank_sets(const char *call, bool plain, int n_sets, const int64_t *t_set, int J, const int *index, const float *weight, const int *onset);
     // the scene reverb (scene_reverb.cpp, kernels_reverb.hip): a caller's n_in bus signals through K taps per (output channel, input)
     int scene_reverb_enable(int n_in, int n_out, int n_taps, int xfade_samples);
     int scene_reverb_set(const float *taps);

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -110,6 +111,8 @@ struct pbso_group {
     int fir_c = 0, fir_k = 0, fir_max_onset = 0;         // the scene filter mix (pbso_group_scene_fir_enable)
     int fir_max_delay = 0;                               // ... its delay stage (pbso_group_scene_fir_delay_enable)
     bool fir_delay_on = false;
+    int fir_bank_f = 0;                                  // ... its bank (pbso_group_scene_fir_bank_create): F, and A = max |tap|
+    double fir_bank_a = 0.0;
     bool fir_on = false, fir_mixed = false;              // ... and whether the last step has had its PBSO_GATHER_FIR
     bool use_rccl = false;                               // a communicator exists: the collectives go through librccl
     bool loopback() const { return transport == PBSO_GROUP_LOOPBACK; }
@@ -621,7 +624,8 @@ int pbso_group_scene_fir_enable(pbso_group *g, int n_channels, int n_taps, int m
     g->fir_c = n_channels;
     g->fir_k = n_taps;
     g->fir_max_onset = max_onset;
-    g->fir_delay_on = false;                             // (a new enable drops the delay stage with everything else)
+    g->fir_delay_on = false;                             // (a new enable drops the delay stage and the bank with everything else)
+    g->fir_bank_f = 0;
     g->fir_mixed = true;                                 // (armed for the next step, as every engine is)
     return PBSO_OK;
 }
@@ -759,6 +763,99 @@ int pbso_group_scene_fir_clear_schedule(pbso_group *g) {
     for (Rank &rk : g->ranks)
         if (rk.n_local > 0) GENG(g, rk, pbso_scene_fir_clear_schedule(rk.eng));
     return PBSO_OK;
+}
+
+// the filter mix's bank: the whole bank on every rank (any object may use any filter)
+int pbso_group_scene_fir_bank_create(pbso_group *g, int n_filters, const float *taps) {
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, "scene_fir_bank_create: the group's scene filter mix is not enabled");
+    if (n_filters < 1 || n_filters > pbso::SCENE_FIR_BANK_MAX_FILTERS) return gfail(g, PBSO_ERR_INVALID, "scene_fir_bank_create: n_filters must be 1 .. 1 << 20");
+    if (!taps) return gfail(g, PBSO_ERR_INVALID, "scene_fir_bank_create: taps is NULL");
+    double A = 0.0;
+    for (size_t i = 0; i < (size_t)n_filters * g->fir_c * g->fir_k; ++i) {
+        if (!std::isfinite(taps[i])) return gfail(g, PBSO_ERR_INVALID, "scene_fir_bank_create: a tap is not finite");
+        A = std::max(A, (double)std::fabs(taps[i]));
+    }
+    // rank by rank, as every enable of the group: should a rank fail, the ranks before it hold the new bank and the others the old
+    // one or none, so the group counts itself as without a bank (bank sets are refused) until a create succeeds on every rank
+    const int had = g->fir_bank_f;
+    g->fir_bank_f = 0;
+    bool first = true;
+    for (Rank &rk : g->ranks)
+        if (rk.n_local > 0) {
+            const int rc = pbso_scene_fir_bank_create(rk.eng, n_filters, taps);
+            // (a refusal by the first rank -- bank sets pending -- is every rank's, and nothing has changed: the old bank stands)
+            if (rc < 0 && first) g->fir_bank_f = had;
+            GENG(g, rk, rc);
+            first = false;
+        }
+    g->fir_bank_f = n_filters;
+    g->fir_bank_a = A;
+    return PBSO_OK;
+}
+
+// bank sets: every rank takes the pairs and onsets of its own objects, a contiguous slice of every set (the arrays are object-major).
+// The values are checked for the whole job first; the times and the state by the engines, which hold one clock and one pending
+// list: the first rank's refusal is every rank's, and no rank has taken anything by then.  `plain`: the set that waits for the next mix.
+static int group_scene_fir_bank_sets(pbso_group *g, const char *call, int n_sets, const int64_t *t_set, bool plain, int J, const int *index,
+                                     const float *weight, const int *onset) {
+    const std::string name(call);
+    if (!g || !g->fir_on) return gfail(g, PBSO_ERR_STATE, name + ": the group's scene filter mix is not enabled");
+    if (g->fir_bank_f == 0) return gfail(g, PBSO_ERR_STATE, name + ": no bank (pbso_group_scene_fir_bank_create)");
+    if (n_sets < 0) return gfail(g, PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!plain && !t_set) return gfail(g, PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!index) return gfail(g, PBSO_ERR_INVALID, name + ": index is NULL");
+    if (!weight) return gfail(g, PBSO_ERR_INVALID, name + ": weight is NULL");
+    if (J < 1 || J > pbso::SCENE_FIR_BANK_MAX_J) return gfail(g, PBSO_ERR_INVALID, name + ": J must be 1 .. 8");
+    const size_t n = (size_t)g->n_objects, nj = (size_t)J;
+    for (size_t r = 0; r < (size_t)n_sets * n; ++r) {
+        double sum = 0.0;
+        for (size_t j = 0; j < nj; ++j) {
+            if (index[r * nj + j] < 0 || index[r * nj + j] >= g->fir_bank_f) return gfail(g, PBSO_ERR_INVALID, name + ": an index is outside [0, n_filters)");
+            if (!std::isfinite(weight[r * nj + j])) return gfail(g, PBSO_ERR_INVALID, name + ": a weight is not finite");
+            sum += std::fabs((double)weight[r * nj + j]);
+        }
+        if (!(sum * g->fir_bank_a <= (double)FLT_MAX))
+            return gfail(g, PBSO_ERR_INVALID, name + ": an object's sum of |weight| times the bank's largest |tap| exceeds FLT_MAX");
+    }
+    if (onset)
+        for (size_t i = 0; i < (size_t)n_sets * n; ++i)
+            if (onset[i] < 0 || onset[i] > g->fir_max_onset) return gfail(g, PBSO_ERR_INVALID, name + ": an onset is outside [0, max_onset]");
+    try {
+        std::vector<int> is, os;
+        std::vector<float> ws;
+        for (Rank &rk : g->ranks) {
+            if (rk.n_local == 0) continue;
+            const size_t lo = (size_t)g->cuts[rk.rank], nl = (size_t)rk.n_local;
+            is.resize((size_t)n_sets * nl * nj);
+            ws.resize((size_t)n_sets * nl * nj);
+            os.resize(onset ? (size_t)n_sets * nl : 0);
+            for (size_t k = 0; k < (size_t)n_sets; ++k) {
+                std::copy(index + (k * n + lo) * nj, index + (k * n + lo + nl) * nj, is.begin() + k * nl * nj);
+                std::copy(weight + (k * n + lo) * nj, weight + (k * n + lo + nl) * nj, ws.begin() + k * nl * nj);
+                if (onset) std::copy(onset + k * n + lo, onset + k * n + lo + nl, os.begin() + k * nl);
+            }
+            const int *op = onset ? os.data() : nullptr;
+            GENG(g, rk, plain ? pbso_scene_fir_set_bank(rk.eng, J, is.data(), ws.data(), op)
+                              : pbso_scene_fir_bank_schedule(rk.eng, n_sets, t_set, J, is.data(), ws.data(), op));
+        }
+    } catch (const std::exception &ex) {
+        return gfail(g, PBSO_ERR_NOMEM, ex.what());
+    }
+    return PBSO_OK;
+}
+
+int pbso_group_scene_fir_set_bank(pbso_group *g, int J, const int *index, const float *weight, const int *onset) {
+    return group_scene_fir_bank_sets(g, "scene_fir_set_bank", 1, nullptr, true, J, index, weight, onset);
+}
+
+int pbso_group_scene_fir_set_bank_at(pbso_group *g, int64_t t_set, int J, const int *index, const float *weight, const int *onset) {
+    return group_scene_fir_bank_sets(g, "scene_fir_set_bank_at", 1, &t_set, false, J, index, weight, onset);
+}
+
+int pbso_group_scene_fir_bank_schedule(pbso_group *g, int n_sets, const int64_t *t_set, int J, const int *index, const float *weight,
+                                       const int *onset) {
+    return group_scene_fir_bank_sets(g, "scene_fir_bank_schedule", n_sets, t_set, false, J, index, weight, onset);
 }
 
 // point-to-point transfers in pieces of at most 256 MB: a 1.8 GB ncclSend / ncclRecv pair of a rank to itself (1024 objects x ten seconds

@@ -375,6 +375,14 @@ constexpr int SCENE_FIR_MAX_TAPS = 1024;
 int scene_fir_padded_taps(int K);                        // floats of one (channel, object) row of the padded reversed taps
 // P[n_co][scene_fir_padded_taps(K)] from taps[n_co][K] (n_co = C * n_obj rows)
 int launch_scene_fir_prepare(const float *taps, long long n_co, int K, float *P, hipStream_t stream);
+// The same rows from a bank (pbso_scene_fir_bank_create; kernels_fir_bank.hip), for n_sets bank sets in one launch: set s, of
+// hdr[s][1] = J (index, weight) pairs per object, is written to pool[hdr[s][0]][C][n_obj][LP], every tap
+// acc = 0.f; j ascending: acc = fmaf(weight[s][o][j], bank[index[s][o][j]][c][k], acc).  bank [F][C][K]; index / weight
+// [n_sets][n_obj][Jmax] with the first J of a row read; every index in [0, F) (the host's validation).
+constexpr int SCENE_FIR_BANK_MAX_J = 8;
+constexpr int SCENE_FIR_BANK_MAX_FILTERS = 1 << 20;
+int launch_scene_fir_bank_prepare(const float *bank, const int *hdr, const int *index, const float *weight, int n_sets, int Jmax,
+                                  int n_obj, int C, int K, float *pool, hipStream_t stream);
 // out[c][i] = Yto_c(t0 + i), i < n; for i < n_fade (the part of a cross-fade in this step; then R >= 2 and the *_from arrays are
 // read) Yfrom + w (Yto - Yfrom), w = (float)((double)(t0 + i - t_set + 1) / (double)R).  rows [n_obj][n]; hist [n_obj][H] the H
 // samples before it; parts: 2 x C x mix_objects_groups(n_obj) x n floats.  P_to NULL (nothing set yet): silence.  Then hist_next =

@@ -9,9 +9,13 @@
 // launched as it always was.
 // The optional delay stage (pbso_scene_fir_delay_enable) puts the scene mix's ramped fractional delay per
 // object in front of the filters: its records, the second history (of x: `hist` then holds z), and the other launch.
+// The bank (pbso_scene_fir_bank_create): F filters that stay on the device; a bank set -- J (index, weight) pairs per object --
+// waits on the host exactly as a taps set does, in the same pending list, and the mix that takes it has its taps built on the
+// device (kernels_fir_bank.hip) where a taps set's are copied and reversed.  From there on nothing knows the difference.
 #include "bus_state.h"
 #include "fir_schedule.h"
 
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -62,9 +66,12 @@ struct SceneFir {
     int C = 0, N = 0, K = 0, max_onset = 0, H = 0, LP = 0;          // H = max_onset + K - 1 samples of history per object
     XFade fade;                                          // which set is in force, which is faded out, since when
     std::vector<int> onset_to, onset_from;
-    // a set call waits here for the next mix (a later one replaces it)
+    // a set call waits here for the next mix (a later one replaces it): taps, or pend_J > 0 pairs per object into the bank
     std::vector<float> pend_taps;
     std::vector<int> pend_onset;
+    int pend_J = 0;
+    std::vector<int> pend_index;                         // [N][pend_J]
+    std::vector<float> pend_weight;
     StepClock clock;
     int64_t n_mixes = 0, n_sets = 0;
     HistPair hist;                                       // [N][H]: of x, or of z = the delayed x once the delay stage is enabled
@@ -75,10 +82,17 @@ struct SceneFir {
     // taps of an upload
     DevMem<float> d_P[2], d_raw;
     DevMem<int> d_onset[2];
-    UploadRing up;                                       // blocks of taps [C][N][K], then onsets [N]
+    UploadRing up;                                       // blocks of taps [C][N][K] (or a bank set: bank_set_bytes), then onsets [N]
+    // the bank [F][C][K]; A = max |tap| of it; where a plain bank set lies on the device: (slot, J) | index [N][J] | weight [N][J]
+    DevMem<float> d_bank;
+    int bank_F = 0;
+    double bank_A = 0.0;
+    int64_t n_bank_sets = 0;
+    DevMem<char> d_bset;
     // the schedule: the filter sets not yet in force as given (onset NULL resolved to the predecessor's), ascending in t, none
     // before the clock and none inside its predecessor's fade
-    struct Pending { long long t; std::vector<float> taps; std::vector<int> onset; };
+    // (a bank set: J > 0 pairs per object, index / weight [N][J], and no taps)
+    struct Pending { long long t; std::vector<float> taps; std::vector<int> onset; int J = 0; std::vector<int> index; std::vector<float> weight; };
     std::deque<Pending> sched;
     StagingRing stage;                                   // a step's times, work strips, onsets, delays and taps
     DevMem<char> d_sets;                                 // ... on the device
@@ -86,6 +100,12 @@ struct SceneFir {
     DevMem<int> d_onpool;                                // ... and onsets [S + 2][N]
 
     size_t taps_floats() const { return (size_t)C * N * K; }
+    static size_t bank_set_bytes(int n, int J) { return 2 * sizeof(int) + (size_t)n * J * (sizeof(int) + sizeof(float)); }
+    size_t bank_sets_pending() const {
+        size_t k = fade.pending && pend_J > 0 ? 1 : 0;
+        for (const Pending &q : sched) k += q.J > 0 ? 1 : 0;
+        return k;
+    }
 };
 
 static const BusWords WORDS = {"scene_fir", "mixed", "the mixer", "audio", "mix", "n_channels"};
@@ -129,7 +149,7 @@ int Engine::scene_fir_enable(int C, int K, int max_onset, int xfade) {
         if (m->d_onset[i].alloc(no) != hipSuccess) return nomem("the onsets");
     }
     if (m->d_raw.alloc(cn * K) != hipSuccess) return nomem("the taps");
-    switch (m->up.create(cn * K * sizeof(float) + no * sizeof(int))) {
+    switch (m->up.create(std::max(cn * K * sizeof(float), SceneFir::bank_set_bytes((int)no, SCENE_FIR_BANK_MAX_J)) + no * sizeof(int))) {
     case UploadRing::NO_MEMORY: return nomem("the upload ring");
     case UploadRing::NO_EVENT: return hip_fail(hipErrorInvalidValue, "scene_fir_enable: hipEventCreate");
     case UploadRing::OK: break;
@@ -156,6 +176,7 @@ int Engine::scene_fir_set(const float *taps, const int *onset) {
     if (onset) m.pend_onset.assign(onset, onset + m.N);
     else if (!m.fade.pending) m.pend_onset = m.onset_to;
     m.pend_taps.assign(taps, taps + nt);
+    m.pend_J = 0;
     m.fade.pending = true;
     ++m.n_sets;
     return PBSO_OK;
@@ -184,15 +205,32 @@ int Engine::scene_fir(void *d_out) {
         // on the stream)
         char *h_up;
         HIPTRY(m.up.acquire(h_up));
-        const size_t tb = m.taps_floats() * sizeof(float), ob = (size_t)m.N * sizeof(int);
-        std::memcpy(h_up, m.pend_taps.data(), tb);
-        std::memcpy(h_up + tb, m.pend_onset.data(), ob);
+        const size_t ob = (size_t)m.N * sizeof(int);
         const int dst = f.incoming();
-        HIPTRY(hipMemcpyAsync(m.d_raw, h_up, tb, hipMemcpyHostToDevice, stream_));
-        HIPTRY(hipMemcpyAsync(m.d_onset[dst], h_up + tb, ob, hipMemcpyHostToDevice, stream_));
-        HIPTRY(m.up.record(stream_));
-        const int prc = launch_scene_fir_prepare(m.d_raw, (long long)m.C * m.N, m.K, m.d_P[dst], stream_);
-        if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_prepare");
+        if (m.pend_J > 0) {
+            // a bank set: its pairs go up instead of taps, and the taps are built where they are read (d_raw is not used)
+            const int J = m.pend_J, hdr[2] = {0, J};
+            const size_t ib = (size_t)m.N * J * sizeof(int), bb = SceneFir::bank_set_bytes(m.N, J);
+            std::memcpy(h_up, hdr, sizeof(hdr));
+            std::memcpy(h_up + sizeof(hdr), m.pend_index.data(), ib);
+            std::memcpy(h_up + sizeof(hdr) + ib, m.pend_weight.data(), (size_t)m.N * J * sizeof(float));
+            std::memcpy(h_up + bb, m.pend_onset.data(), ob);
+            HIPTRY(hipMemcpyAsync(m.d_bset, h_up, bb, hipMemcpyHostToDevice, stream_));
+            HIPTRY(hipMemcpyAsync(m.d_onset[dst], h_up + bb, ob, hipMemcpyHostToDevice, stream_));
+            HIPTRY(m.up.record(stream_));
+            const int prc = launch_scene_fir_bank_prepare(m.d_bank, (const int *)m.d_bset.p, (const int *)(m.d_bset.p + sizeof(hdr)),
+                                                          (const float *)(m.d_bset.p + sizeof(hdr) + ib), 1, J, m.N, m.C, m.K, m.d_P[dst], stream_);
+            if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_bank_prepare");
+        } else {
+            const size_t tb = m.taps_floats() * sizeof(float);
+            std::memcpy(h_up, m.pend_taps.data(), tb);
+            std::memcpy(h_up + tb, m.pend_onset.data(), ob);
+            HIPTRY(hipMemcpyAsync(m.d_raw, h_up, tb, hipMemcpyHostToDevice, stream_));
+            HIPTRY(hipMemcpyAsync(m.d_onset[dst], h_up + tb, ob, hipMemcpyHostToDevice, stream_));
+            HIPTRY(m.up.record(stream_));
+            const int prc = launch_scene_fir_prepare(m.d_raw, (long long)m.C * m.N, m.K, m.d_P[dst], stream_);
+            if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_prepare");
+        }
         m.onset_from.swap(m.onset_to);
         m.onset_to = m.pend_onset;
         f.swap_in(t);
@@ -352,6 +390,19 @@ static FirPredecessor fir_predecessor(const SceneFir &m) {
     if (m.fade.pending) return {true, m.clock.t, m.clock.t + 1};
     return {m.fade.have_to, m.fade.t_set, m.clock.t};
 }
+// why the times of n_sets scheduled filter sets (taps or bank sets: one kind, one pending list) are refused; nullptr: they pass
+static const char *fir_times_refused(const SceneFir &m, int n_sets, const int64_t *t_set) {
+    FirPredecessor prev = fir_predecessor(m);
+    for (int k = 0; k < n_sets; ++k) {
+        const long long t = (long long)t_set[k];
+        if (t < m.clock.t) return ": a t_set lies before the next mixed sample";
+        if (t < prev.floor) return ": the t_set are not ascending behind the last pending set's";
+        if (prev.have && !fir_spacing_ok(t, prev.t, m.fade.R))
+            return ": a t_set lies inside the cross-fade of the set before it (pbso_scene_fir_schedule_info tells the first that may follow)";
+        prev = {true, t, t + 1};
+    }
+    return nullptr;
+}
 static long long fir_delay_floor(const SceneFir &m, const FirDelay &d) {
     return !d.sched.empty() ? d.sched.back().t + 1 : (d.have_pend ? m.clock.t + 1 : m.clock.t);
 }
@@ -366,15 +417,7 @@ int Engine::scene_fir_schedule(const char *call, int n_sets, const int64_t *t_se
     if (!t_set) return fail(PBSO_ERR_INVALID, name + ": t_set is NULL");
     if (!taps) return fail(PBSO_ERR_INVALID, name + ": taps is NULL");
     SceneFir &m = *fir_;
-    FirPredecessor prev = fir_predecessor(m);
-    for (int k = 0; k < n_sets; ++k) {
-        const long long t = (long long)t_set[k];
-        if (t < m.clock.t) return fail(PBSO_ERR_INVALID, name + ": a t_set lies before the next mixed sample");
-        if (t < prev.floor) return fail(PBSO_ERR_INVALID, name + ": the t_set are not ascending behind the last pending set's");
-        if (prev.have && !fir_spacing_ok(t, prev.t, m.fade.R))
-            return fail(PBSO_ERR_INVALID, name + ": a t_set lies inside the cross-fade of the set before it (pbso_scene_fir_schedule_info tells the first that may follow)");
-        prev = {true, t, t + 1};
-    }
+    if (const char *why = fir_times_refused(m, n_sets, t_set)) return fail(PBSO_ERR_INVALID, name + why);
     const size_t nt = m.taps_floats();
     for (size_t i = 0; i < (size_t)n_sets * nt; ++i)
         if (!std::isfinite(taps[i])) return fail(PBSO_ERR_INVALID, name + ": a tap is not finite");
@@ -446,6 +489,118 @@ int Engine::scene_fir_schedule_info(int64_t out[4]) {
     return PBSO_OK;
 }
 
+// ---- the bank
+
+// F filters of [C][K] taps, on the device from here on.  A second create replaces the first, unless bank sets are waiting for it.
+int Engine::scene_fir_bank_create(int F, const float *taps) {
+    if (!fir_) return fail(PBSO_ERR_STATE, "scene_fir_bank_create: the scene filter mix is not enabled");
+    if (F < 1 || F > SCENE_FIR_BANK_MAX_FILTERS) return fail(PBSO_ERR_INVALID, "scene_fir_bank_create: n_filters must be 1 .. 1 << 20");
+    if (!taps) return fail(PBSO_ERR_INVALID, "scene_fir_bank_create: taps is NULL");
+    SceneFir &m = *fir_;
+    if ((long long)m.N * (m.LP / 4) > 0x7fffffffLL)
+        return fail(PBSO_ERR_INVALID, "scene_fir_bank_create: n_objects * LP / 4 does not fit 31 bits");
+    if (m.bank_sets_pending()) return fail(PBSO_ERR_STATE, "scene_fir_bank_create: bank sets are pending (pbso_scene_fir_clear_schedule drops the scheduled ones)");
+    const size_t nf = (size_t)F * m.C * m.K;
+    double A = 0.0;
+    for (size_t i = 0; i < nf; ++i) {
+        if (!std::isfinite(taps[i])) return fail(PBSO_ERR_INVALID, "scene_fir_bank_create: a tap is not finite");
+        A = std::max(A, (double)std::fabs(taps[i]));
+    }
+    HIPTRY(hipSetDevice(desc_.device));
+    auto nomem = [&]() {
+        (void)hipGetLastError();
+        return fail(PBSO_ERR_NOMEM, "scene_fir_bank_create: cannot allocate the bank");
+    };
+    DevMem<float> bank;
+    if (bank.alloc(nf) != hipSuccess) return nomem();
+    if (!m.d_bset.p && m.d_bset.alloc(SceneFir::bank_set_bytes(std::max(m.N, 1), SCENE_FIR_BANK_MAX_J)) != hipSuccess) return nomem();
+    // (behind whatever still reads the bank replaced; it is freed once the stream is idle)
+    HIPTRY(hipMemcpyAsync(bank.p, taps, nf * sizeof(float), hipMemcpyHostToDevice, stream_));
+    HIPTRY(hipStreamSynchronize(stream_));
+    std::swap(m.d_bank.p, bank.p);
+    std::swap(m.d_bank.cap, bank.cap);
+    m.bank_F = F;
+    m.bank_A = A;
+    return PBSO_OK;
+}
+
+int Engine::scene_fir_bank_info(int64_t out[4]) {
+    if (!fir_) return fail(PBSO_ERR_STATE, "scene_fir_bank_info: the scene filter mix is not enabled");
+    if (!out) return fail(PBSO_ERR_INVALID, "scene_fir_bank_info: out is NULL");
+    const SceneFir &m = *fir_;
+    out[0] = m.bank_F;
+    out[1] = SCENE_FIR_BANK_MAX_J;
+    out[2] = m.n_bank_sets;
+    out[3] = (int64_t)((size_t)m.bank_F * m.C * m.K * sizeof(float));
+    return PBSO_OK;
+}
+
+// n_sets bank sets: index / weight [n_sets][N][J], onset [n_sets][N] or NULL.  `plain`: the plain set (n_sets is 1, no t_set), which
+// waits for the next mix by pbso_scene_fir_set's rules; else scheduled ones, by pbso_scene_fir_schedule's.  From the checks on a
+// bank set is a filter set like any other.  All of them are checked before the first is taken.
+int Engine::scene_fir_bank_sets(const char *call, bool plain, int n_sets, const int64_t *t_set, int J, const int *index, const float *weight, const int *onset) {
+    const std::string name(call);
+    if (!fir_) return fail(PBSO_ERR_STATE, name + ": the scene filter mix is not enabled");
+    SceneFir &m = *fir_;
+    if (!m.d_bank.p) return fail(PBSO_ERR_STATE, name + ": no bank (pbso_scene_fir_bank_create)");
+    if (n_sets < 0) return fail(PBSO_ERR_INVALID, name + ": n_sets is negative");
+    if (n_sets == 0) return PBSO_OK;
+    if (!plain && !t_set) return fail(PBSO_ERR_INVALID, name + ": t_set is NULL");
+    if (!index) return fail(PBSO_ERR_INVALID, name + ": index is NULL");
+    if (!weight) return fail(PBSO_ERR_INVALID, name + ": weight is NULL");
+    if (J < 1 || J > SCENE_FIR_BANK_MAX_J) return fail(PBSO_ERR_INVALID, name + ": J must be 1 .. 8");
+    if (plain) {
+        if (!m.sched.empty()) return fail(PBSO_ERR_STATE, name + ": scheduled sets are pending (pbso_scene_fir_clear_schedule drops them)");
+        if (m.fade.fading(m.clock.t))
+            return fail(PBSO_ERR_STATE, name + ": the cross-fade of the last set is still running (pbso_scene_fir_info tells when it ends)");
+    } else if (const char *why = fir_times_refused(m, n_sets, t_set))
+        return fail(PBSO_ERR_INVALID, name + why);
+    const size_t np = (size_t)m.N * J;                   // pairs of one set
+    for (size_t r = 0; r < (size_t)n_sets * m.N; ++r) {  // one object of one set
+        double sum = 0.0;
+        for (int j = 0; j < J; ++j) {
+            const int i = index[r * J + j];
+            const float w = weight[r * J + j];
+            if (i < 0 || i >= m.bank_F) return fail(PBSO_ERR_INVALID, name + ": an index is outside [0, n_filters)");
+            if (!std::isfinite(w)) return fail(PBSO_ERR_INVALID, name + ": a weight is not finite");
+            sum += std::fabs((double)w);
+        }
+        // every partial sum of the chain and every tap stay finite
+        if (!(sum * m.bank_A <= (double)FLT_MAX))
+            return fail(PBSO_ERR_INVALID, name + ": an object's sum of |weight| times the bank's largest |tap| exceeds FLT_MAX");
+    }
+    if (onset)
+        for (size_t i = 0; i < (size_t)n_sets * m.N; ++i)
+            if (onset[i] < 0 || onset[i] > m.max_onset) return fail(PBSO_ERR_INVALID, name + ": an onset is outside [0, max_onset]");
+    if (plain) {
+        // takes effect at the first sample of the next mixed step; onset NULL keeps the onsets last set (0 at first)
+        if (onset) m.pend_onset.assign(onset, onset + m.N);
+        else if (!m.fade.pending) m.pend_onset = m.onset_to;
+        m.pend_index.assign(index, index + np);
+        m.pend_weight.assign(weight, weight + np);
+        m.pend_J = J;
+        m.pend_taps.clear();
+        m.fade.pending = true;
+    } else {
+        std::deque<SceneFir::Pending> taken;             // (built apart: a failed allocation leaves the pending list as it was)
+        const std::vector<int> *on_prev = !m.sched.empty() ? &m.sched.back().onset : (m.fade.pending ? &m.pend_onset : &m.onset_to);
+        for (int k = 0; k < n_sets; ++k) {
+            SceneFir::Pending q{(long long)t_set[k], {}, {}};
+            q.J = J;
+            q.index.assign(index + (size_t)k * np, index + (size_t)(k + 1) * np);
+            q.weight.assign(weight + (size_t)k * np, weight + (size_t)(k + 1) * np);
+            if (onset) q.onset.assign(onset + (size_t)k * m.N, onset + (size_t)(k + 1) * m.N);
+            else q.onset = *on_prev;
+            taken.push_back(std::move(q));
+            on_prev = &taken.back().onset;
+        }
+        for (SceneFir::Pending &q : taken) m.sched.push_back(std::move(q));
+    }
+    m.n_sets += n_sets;
+    m.n_bank_sets += n_sets;
+    return PBSO_OK;
+}
+
 // A step with scheduled sets inside it.  A plain set still waiting for this mix takes effect at the step's first sample: it goes
 // in front of the scheduled ones (which lie behind it) as one more set of its kind.  Everything that can refuse comes before
 // anything is taken or launched.
@@ -476,11 +631,26 @@ int Engine::scene_fir_scheduled_step(void *d_out) {
     fir_strips(segs, t, f.R, strip, strips);
     bool any_from = false;
     for (const FirStrip &e : strips) any_from = any_from || e.set_from >= 0;
-    // one staged block: filter times | delay times | strips | onsets [S][N] | delays [K_d][N] | taps [S][C][N][K]
-    const size_t cn = (size_t)m.C * m.N, nt = m.taps_floats(), set_floats = cn * m.LP;
+    // which of the step's sets are bank sets (the others bring taps), and the widest of those
+    std::vector<const SceneFir::Pending *> sets;         // of the step, in order; nullptr: the plain set waiting for this mix
+    if (f.pending) sets.push_back(nullptr);
+    for (size_t k = 0; k < Ss; ++k) sets.push_back(&m.sched[k]);
+    auto J_of = [&](size_t k) { return sets[k] ? sets[k]->J : m.pend_J; };
+    size_t Sb = 0;
+    int Jmax = 0;
+    for (size_t k = 0; k < S; ++k)
+        if (J_of(k) > 0) {
+            ++Sb;
+            Jmax = std::max(Jmax, J_of(k));
+        }
+    const size_t St = S - Sb;
+    // one staged block: filter times | delay times | strips | onsets [S][N] | delays [K_d][N] | of the S_b bank sets: (pool slot, J)
+    // [S_b][2], index [S_b][N][Jmax], weight [S_b][N][Jmax] | taps [S_t][C][N][K] of the others
+    const size_t cn = (size_t)m.C * m.N, nt = m.taps_floats(), set_floats = cn * m.LP, npair = (size_t)m.N * Jmax;
     const size_t off_td = S * sizeof(long long), off_strips = off_td + Kd * sizeof(long long),
                  off_on = off_strips + strips.size() * sizeof(FirStrip), off_dl = off_on + S * m.N * sizeof(int),
-                 off_taps = off_dl + Kd * m.N * sizeof(float), set_bytes = off_taps + S * nt * sizeof(float);
+                 off_hdr = off_dl + Kd * m.N * sizeof(float), off_ix = off_hdr + Sb * 2 * sizeof(int), off_w = off_ix + Sb * npair * sizeof(int),
+                 off_taps = off_w + Sb * npair * sizeof(float), set_bytes = off_taps + St * nt * sizeof(float);
     char *h_sets = nullptr;
     GROWTRY(grow(m.d_sets, set_bytes, stream_), "scene_fir: cannot allocate the step's scheduled sets", "scene_fir: scheduled sets");
     GROWTRY(grow(m.d_pool, (S + 2) * set_floats, stream_), "scene_fir: cannot allocate the step's pool of filter sets", "scene_fir: filter pool");
@@ -497,15 +667,27 @@ int Engine::scene_fir_scheduled_step(void *d_out) {
     std::memcpy(h_sets + off_strips, strips.data(), strips.size() * sizeof(FirStrip));
     std::vector<const std::vector<int> *> onsets;        // of the step's sets, in order
     {
-        size_t k = 0;
-        if (f.pending) {
-            std::memcpy(h_sets + off_taps, m.pend_taps.data(), nt * sizeof(float));
-            onsets.push_back(&m.pend_onset);
-            ++k;
-        }
-        for (size_t i = 0; i < Ss; ++i, ++k) {
-            std::memcpy(h_sets + off_taps + k * nt * sizeof(float), m.sched[i].taps.data(), nt * sizeof(float));
-            onsets.push_back(&m.sched[i].onset);
+        size_t k = 0, kt = 0, kb = 0;                    // sets, and those with taps / from the bank among them
+        for (; k < S; ++k) {
+            const SceneFir::Pending *q = sets[k];
+            onsets.push_back(q ? &q->onset : &m.pend_onset);
+            const int J = J_of(k);
+            if (J == 0) {
+                std::memcpy(h_sets + off_taps + (kt++) * nt * sizeof(float), (q ? q->taps : m.pend_taps).data(), nt * sizeof(float));
+                continue;
+            }
+            // pool slot 2 + k; the J pairs of an object in a row of Jmax (the rest is not read)
+            const int hdr[2] = {(int)(2 + k), J}, *ix = (q ? q->index : m.pend_index).data();
+            const float *w = (q ? q->weight : m.pend_weight).data();
+            std::memcpy(h_sets + off_hdr + kb * sizeof(hdr), hdr, sizeof(hdr));
+            int *h_ix = (int *)(h_sets + off_ix) + kb * npair;
+            float *h_w = (float *)(h_sets + off_w) + kb * npair;
+            for (int o = 0; o < m.N; ++o)
+                for (int j = 0; j < Jmax; ++j) {
+                    h_ix[(size_t)o * Jmax + j] = j < J ? ix[(size_t)o * J + j] : 0;
+                    h_w[(size_t)o * Jmax + j] = j < J ? w[(size_t)o * J + j] : 0.f;
+                }
+            ++kb;
         }
         for (k = 0; k < S; ++k) std::memcpy(h_sets + off_on + k * m.N * sizeof(int), onsets[k]->data(), (size_t)m.N * sizeof(int));
         k = 0;
@@ -527,8 +709,24 @@ int Engine::scene_fir_scheduled_step(void *d_out) {
     }
     if (S) {
         HIPTRY(hipMemcpyAsync(m.d_onpool.p + 2 * (size_t)m.N, m.d_sets.p + off_on, S * on_bytes, hipMemcpyDeviceToDevice, stream_));
-        const int prc = launch_scene_fir_prepare((const float *)(m.d_sets.p + off_taps), (long long)(S * cn), m.K, m.d_pool.p + 2 * set_floats, stream_);
-        if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_prepare");
+        // the sets that brought taps: one launch per run of consecutive ones (a step without bank sets is one run: the launch
+        // it always was); the bank sets: one launch for all of them, each to its slot
+        for (size_t k = 0, kt = 0; k < S;) {
+            size_t e = k;
+            while (e < S && J_of(e) == 0) ++e;
+            if (e > k) {
+                const int prc = launch_scene_fir_prepare((const float *)(m.d_sets.p + off_taps) + kt * nt, (long long)((e - k) * cn), m.K,
+                                                         m.d_pool.p + (2 + k) * set_floats, stream_);
+                if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_prepare");
+                kt += e - k;
+            }
+            k = e + (e < S ? 1 : 0);
+        }
+        if (Sb) {
+            const int prc = launch_scene_fir_bank_prepare(m.d_bank, (const int *)(m.d_sets.p + off_hdr), (const int *)(m.d_sets.p + off_ix),
+                                                          (const float *)(m.d_sets.p + off_w), (int)Sb, Jmax, m.N, m.C, m.K, m.d_pool, stream_);
+            if (prc != 0) return hip_fail((hipError_t)prc, "launch_scene_fir_bank_prepare");
+        }
     }
     if (d && d->dirty) {
         char *h_p;

@@ -255,6 +255,39 @@ class Group:
                 return self.engine(rank).scene_fir_schedule_info()
         raise PbsoError(capi.ERR_STATE, "scene_fir_schedule_info: no local rank has objects")
 
+    # ... and the bank: the whole bank on every local rank; index, weight and onset by global id, object-major
+    def scene_fir_bank_create(self, taps):
+        """pbso_group_scene_fir_bank_create: taps [n_filters][n_channels][n_taps] to every local rank"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        assert h.ndim == 3
+        self._chk(self._l.pbso_group_scene_fir_bank_create(self._h, h.shape[0], h.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_bank_info(self):
+        """pbso_scene_fir_bank_info of the first local rank that has objects (every rank holds the whole bank)"""
+        for rank in self.local_ranks():
+            lo, hi = self.span(rank)
+            if hi > lo:
+                return self.engine(rank).scene_fir_bank_info()
+        raise PbsoError(capi.ERR_STATE, "scene_fir_bank_info: no local rank has objects")
+
+    def scene_fir_set_bank(self, index, weight, onset=None):
+        """pbso_group_scene_fir_set_bank: index, weight [n_objects of the job][J], onset [n_objects of the job]"""
+        args, _keep = Engine._bank_pairs(index, weight, onset, 0)
+        self._chk(self._l.pbso_group_scene_fir_set_bank(self._h, *args))
+
+    def scene_fir_set_bank_at(self, t_set, index, weight, onset=None):
+        """pbso_group_scene_fir_set_bank_at: as scene_fir_set_bank, taking effect at the absolute sample t_set"""
+        args, _keep = Engine._bank_pairs(index, weight, onset, 0)
+        self._chk(self._l.pbso_group_scene_fir_set_bank_at(self._h, int(t_set), *args))
+
+    def scene_fir_bank_schedule(self, t_set, index, weight, onset=None):
+        """pbso_group_scene_fir_bank_schedule: t_set [n_sets], index and weight [n_sets][n_objects of the job][J], onset
+        [n_sets][n_objects of the job] or None"""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        args, keep = Engine._bank_pairs(index, weight, onset, 1)
+        assert keep[0].shape[0] == t.size
+        self._chk(self._l.pbso_group_scene_fir_bank_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)), *args))
+
     def sync(self):
         self._chk(self._l.pbso_group_sync(self._h))
 

@@ -748,6 +748,48 @@ class Engine:
         self._chk(self._l.pbso_scene_fir_schedule_info(self._h, v))
         return {"t": v[0], "pending": v[1], "pending_delay": v[2], "next_t_min": v[3]}
 
+    # ... and the bank: the filters stay on the device, a set is J (index, weight) pairs per object
+    def scene_fir_bank_create(self, taps):
+        """pbso_scene_fir_bank_create: taps [n_filters][n_channels][n_taps], finite; a second create replaces the bank"""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        assert h.ndim == 3
+        self._chk(self._l.pbso_scene_fir_bank_create(self._h, h.shape[0], h.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def scene_fir_bank_info(self):
+        """pbso_scene_fir_bank_info: filters in the bank (0: none), the largest J, bank sets accepted, device bytes of the bank"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_scene_fir_bank_info(self._h, v))
+        return {"n_filters": v[0], "max_j": v[1], "sets": v[2], "bytes": v[3]}
+
+    @staticmethod
+    def _bank_pairs(index, weight, onset, lead):
+        """index / weight [*lead][n_objects][J] -> (J, the three arrays as the C ABI takes them)"""
+        i = np.ascontiguousarray(index, dtype=np.int32)
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        d = None if onset is None else np.ascontiguousarray(onset, dtype=np.int32)
+        assert i.ndim == lead + 2 and w.shape == i.shape and (d is None or d.shape == i.shape[:-1])
+        return (i.shape[-1], i.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_float)),
+                None if d is None else d.ctypes.data_as(C.POINTER(C.c_int))), (i, w, d)
+
+    def scene_fir_set_bank(self, index, weight, onset=None):
+        """pbso_scene_fir_set_bank: index, weight [n_objects][J] into the bank, onset [n_objects] ints; as scene_fir_set with the
+        taps acc = fmaf(weight[o][j], bank[index[o][j]][c][k], acc), j ascending"""
+        args, _keep = self._bank_pairs(index, weight, onset, 0)
+        self._chk(self._l.pbso_scene_fir_set_bank(self._h, *args))
+
+    def scene_fir_set_bank_at(self, t_set, index, weight, onset=None):
+        """pbso_scene_fir_set_bank_at: as scene_fir_set_bank, taking effect at the absolute sample t_set"""
+        args, _keep = self._bank_pairs(index, weight, onset, 0)
+        self._chk(self._l.pbso_scene_fir_set_bank_at(self._h, int(t_set), *args))
+
+    def scene_fir_bank_schedule(self, t_set, index, weight, onset=None):
+        """pbso_scene_fir_bank_schedule: t_set [n_sets] ascending absolute samples, index and weight [n_sets][n_objects][J], onset
+        [n_sets][n_objects] ints or None.  All or nothing."""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        args, keep = self._bank_pairs(index, weight, onset, 1)
+        assert keep[0].shape[0] == t.size
+        self._chk(self._l.pbso_scene_fir_bank_schedule(self._h, t.size, t.ctypes.data_as(C.POINTER(C.c_int64)), *args))
+
     # -- scene reverb: n_in device-resident bus signals through K taps per (output channel, input), history kept across steps ----
     def scene_reverb_enable(self, n_in, n_out, n_taps, xfade_samples=0):
         """pbso_scene_reverb_enable: from the next step on, every step is processed exactly once (scene_reverb)"""

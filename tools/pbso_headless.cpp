@@ -42,6 +42,13 @@
 //                    buffer on, cross-faded over N samples (default 441; change points must be at least that far apart).  A taps
 //                    file is raw little-endian float32 [C][K], every file with the same K; every distinct path is loaded once.
 //                    Not together with --pan.
+//   --channels C --fir-bank FILE --fir-taps K --fir-dirs SCRIPT   in place of --fir: the filters come from a bank that is uploaded
+//                    once (pbso_scene_fir_bank_create) -- FILE is raw little-endian float32 [F][C][K], F follows from its size --
+//                    and SCRIPT's lines <buffer> <copy> <onset> <i0> <w0> [<i1> <w1> ... up to 8 pairs] give copy the filter
+//                    sum_j w_j * bank[i_j] (one fmaf per pair, in the line's order) from that buffer on.  A line with fewer
+//                    pairs than the script's widest is padded with (0, 0.f), which adds nothing.  Composes with --xfade,
+//                    --fir-delay, --fir-schedule, --reverb, --limit, --out-rate and --devices exactly as --fir does; not
+//                    together with --fir or --pan.
 //   --fir-delay FILE [--delay-ramp N]    with --fir: the filter mix's delay stage (pbso_scene_fir_delay_enable): lines <buffer> <copy>
 //                    <delay in samples> set copy's fractional delay in front of its filters from that buffer on, ramped over N
 //                    samples (default 441; a moving source's Doppler shift).  max_delay is the file's largest value, rounded
@@ -225,7 +232,7 @@ static void feed_strokes(pbso_engine *e, const StrokeScript &sc, const std::vect
 }
 // --channels / --pan: the scene mix's script
 struct Pan { long b; int copy; std::vector<float> gd; };   // gd: g_0 d_0 ... g_{C-1} d_{C-1}
-struct FirLine { long b; int copy, onset, file; };          // file: index into Scene::fir_files
+struct FirLine { long b; int copy, onset, file; std::vector<std::pair<int, float>> pairs; };   // file: index into Scene::fir_files; pairs: --fir-dirs
 struct FirDelayLine { long b; int copy; float delay; };     // --fir-delay: <buffer> <copy> <delay in samples>
 struct Scene {
     int channels = 0, ramp = 441, copies = 1, max_delay = 0;
@@ -237,6 +244,13 @@ struct Scene {
     int xfade = 441, n_taps = 0, max_onset = 0;
     std::vector<FirLine> fir_lines;
     std::vector<std::vector<float>> fir_files;           // [C][K] each
+    // --fir-bank / --fir-dirs: the filters stay on the device and a line names (index, weight) pairs into them; a copy's pairs as
+    // last set, [copies][bank_J] (a line with fewer pairs than the widest is padded with (0, 0.f), which adds nothing)
+    bool fir_bank = false;
+    std::vector<float> bank;                             // [bank_F][C][K]
+    int bank_F = 0, bank_J = 0;
+    mutable std::vector<int> bank_index;
+    mutable std::vector<float> bank_weight;
     // --fir-delay: the filter mix's delay stage (a ramped fractional delay per copy in front of the filters)
     std::vector<FirDelayLine> fir_delay_lines;
     int fir_max_delay = 0, fir_delay_ramp = 441;
@@ -278,12 +292,16 @@ struct Scene {
         for (long b : at)
             if (set_at(b, gain, delay)) set((int64_t)b * PBSO_FRAMES_PER_BUFFER, gain.data(), delay.data());
     }
-    // ... and taps [C][copies][K], onset [copies]
+    // ... and taps [C][copies][K] (--fir-dirs: bank_index / bank_weight instead), onset [copies]
     bool fir_set_at(long b, std::vector<float> &taps, std::vector<int> &onset) const {
         bool any = false;
         for (const FirLine &p : fir_lines)
             if (p.b == b) {
-                for (int c = 0; c < channels; ++c)
+                for (int j = 0; fir_bank && j < bank_J; ++j) {
+                    bank_index[(size_t)p.copy * bank_J + j] = j < (int)p.pairs.size() ? p.pairs[j].first : 0;
+                    bank_weight[(size_t)p.copy * bank_J + j] = j < (int)p.pairs.size() ? p.pairs[j].second : 0.f;
+                }
+                for (int c = 0; !fir_bank && c < channels; ++c)
                     std::copy(fir_files[p.file].begin() + (size_t)c * n_taps, fir_files[p.file].begin() + (size_t)(c + 1) * n_taps,
                               taps.begin() + ((size_t)c * copies + p.copy) * n_taps);
                 onset[p.copy] = p.onset;
@@ -473,6 +491,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
         const size_t total = (size_t)n_buffers * PBSO_FRAMES_PER_BUFFER;
         if (scene->fir) gcheck(g, pbso_group_scene_fir_enable(g, C, scene->n_taps, scene->max_onset, scene->xfade), "group_scene_fir_enable");
         else gcheck(g, pbso_group_scene_mix_enable(g, C, scene->max_delay, scene->ramp), "group_scene_mix_enable");
+        if (scene->fir_bank) gcheck(g, pbso_group_scene_fir_bank_create(g, scene->bank_F, scene->bank.data()), "group_scene_fir_bank_create");
         if (!scene->fir_delay_lines.empty())
             gcheck(g, pbso_group_scene_fir_delay_enable(g, scene->fir_max_delay, scene->fir_delay_ramp), "group_scene_fir_delay_enable");
         std::vector<float> fir_delay(copies, 0.f);
@@ -486,7 +505,12 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             });
         if (scene->fir_schedule)
             scene->schedule_fir(taps, onset, fir_delay,
-                                [&](int64_t t, const float *h, const int *on) { gcheck(g, pbso_group_scene_fir_set_at(g, t, h, on), "group_scene_fir_set_at"); },
+                                [&](int64_t t, const float *h, const int *on) {
+                                    if (scene->fir_bank)
+                                        gcheck(g, pbso_group_scene_fir_set_bank_at(g, t, scene->bank_J, scene->bank_index.data(), scene->bank_weight.data(), on),
+                                               "group_scene_fir_set_bank_at");
+                                    else gcheck(g, pbso_group_scene_fir_set_at(g, t, h, on), "group_scene_fir_set_at");
+                                },
                                 [&](int64_t t, const float *dl) { gcheck(g, pbso_group_scene_fir_set_delay_at(g, t, dl), "group_scene_fir_set_delay_at"); });
         const std::vector<int> cuts = retune.cut(scene->cuts(n_buffers), n_buffers);
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
@@ -494,7 +518,12 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
             if (scene->fir_schedule) {
                 // (scheduled up front)
             } else if (scene->fir) {
-                if (scene->fir_set_at(cuts[k], taps, onset)) gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
+                if (scene->fir_set_at(cuts[k], taps, onset)) {
+                    if (scene->fir_bank)
+                        gcheck(g, pbso_group_scene_fir_set_bank(g, scene->bank_J, scene->bank_index.data(), scene->bank_weight.data(), onset.data()),
+                               "group_scene_fir_set_bank");
+                    else gcheck(g, pbso_group_scene_fir_set(g, taps.data(), onset.data()), "group_scene_fir_set");
+                }
                 if (scene->fir_delay_set_at(cuts[k], fir_delay)) gcheck(g, pbso_group_scene_fir_set_delay(g, fir_delay.data()), "group_scene_fir_set_delay");
             } else if (scene->pan_schedule) {
                 // (scheduled up front)
@@ -535,7 +564,7 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
 }
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_delay, reverb, strokes_file, arprm_arg, retune_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_dirs, fir_bank, fir_delay, reverb, strokes_file, arprm_arg, retune_arg;
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1, time_chunks = 0;
     Scene scene;
@@ -579,6 +608,9 @@ int main(int argc, char **argv) {
         else if (a == "--retune") retune_arg = val();
         else if (a == "--ramp") scene.ramp = std::atoi(val().c_str());
         else if (a == "--fir") fir = val();
+        else if (a == "--fir-dirs") fir_dirs = val();
+        else if (a == "--fir-bank") fir_bank = val();
+        else if (a == "--fir-taps") scene.n_taps = std::atoi(val().c_str());
         else if (a == "--fir-delay") fir_delay = val();
         else if (a == "--xfade") scene.xfade = std::atoi(val().c_str());
         else if (a == "--delay-ramp") scene.fir_delay_ramp = std::atoi(val().c_str());
@@ -785,6 +817,14 @@ int main(int argc, char **argv) {
     }
     RetuneScript retune;
     if (!retune_arg.empty()) retune.read(retune_arg, devices.empty() ? 1 : copies, n_buffers);
+    // --fir-dirs is --fir with another kind of line: everything below that asks for --fir is answered by it
+    if (!fir_dirs.empty() && (!fir.empty() || !pan.empty())) die("--fir-dirs excludes --fir and --pan: one script sets the filters");
+    if (fir_dirs.empty() != fir_bank.empty()) die("--fir-bank FILE --fir-taps K and --fir-dirs SCRIPT go together");
+    if (fir_dirs.empty() && scene.n_taps != 0) die("--fir-taps belongs to --fir-bank: taps files tell their own length");
+    if (!fir_dirs.empty()) {
+        fir = fir_dirs;
+        scene.fir_bank = true;
+    }
     const bool mixed = scene.channels != 0 || !pan.empty() || !fir.empty();
     if (!pan.empty() && !fir.empty()) die("--pan and --fir exclude each other: one mixer writes the WAV");
     if (scene.pan_schedule && pan.empty()) die("--pan-schedule needs --pan FILE: it schedules that script's lines");
@@ -796,6 +836,19 @@ int main(int argc, char **argv) {
         if (scene.xfade < 0 || scene.xfade > (1 << 20)) die("--xfade must be 0 .. 1048576");
         scene.fir = true;
         scene.copies = devices.empty() ? 1 : copies;
+        if (scene.fir_bank) {
+            // the bank: raw little-endian f32 [F][--channels][--fir-taps]; F follows from the file's size
+            if (scene.n_taps < 1 || scene.n_taps > 1024) die("--fir-taps must be 1 .. 1024");
+            std::ifstream bf(fir_bank, std::ios::binary);
+            if (!bf) die("cannot read bank file " + fir_bank);
+            const std::string bytes((std::istreambuf_iterator<char>(bf)), std::istreambuf_iterator<char>());
+            const size_t per = (size_t)scene.channels * scene.n_taps * 4;
+            if (bytes.empty() || bytes.size() % per != 0 || bytes.size() / per > ((size_t)1 << 20))
+                die("bank file " + fir_bank + " is not float32 [F][--channels][--fir-taps] with F 1 .. 1048576 (" + std::to_string(bytes.size()) + " bytes)");
+            scene.bank_F = (int)(bytes.size() / per);
+            scene.bank.resize(bytes.size() / 4);
+            std::memcpy(scene.bank.data(), bytes.data(), bytes.size());
+        }
         std::ifstream f(fir);
         if (!f) die("cannot read " + fir);
         std::vector<std::string> paths;
@@ -805,12 +858,30 @@ int main(int argc, char **argv) {
             std::istringstream iss(line);
             FirLine p;
             std::string path;
-            if (!(iss >> p.b >> p.copy >> p.onset >> path)) die("bad fir line (<buffer> <copy> <onset> <taps file>): " + line);
+            if (scene.fir_bank) {
+                // --fir-dirs: <buffer> <copy> <onset> <i0> <w0> [<i1> <w1> ... up to 8 pairs]
+                if (!(iss >> p.b >> p.copy >> p.onset)) die("bad fir-dirs line (<buffer> <copy> <onset> <index> <weight> ...): " + line);
+                // (every token is parsed whole: "0.5" where an index belongs is refused, not read as index 0 and weight .5)
+                std::string ti, tw;
+                while (iss >> ti) {
+                    if (!(iss >> tw)) die("fir-dirs line with an index that has no weight: " + line);
+                    char *end = nullptr;
+                    const long ix = std::strtol(ti.c_str(), &end, 10);
+                    if (end == ti.c_str() || *end != '\0') die("fir-dirs index is not an integer (pairs of <index> <weight>): " + line);
+                    const float w = std::strtof(tw.c_str(), &end);
+                    if (end == tw.c_str() || *end != '\0') die("fir-dirs weight is not a number (pairs of <index> <weight>): " + line);
+                    if (ix < 0 || ix >= scene.bank_F) die("fir-dirs index outside the bank's 0 .. " + std::to_string(scene.bank_F - 1) + ": " + line);
+                    if (!std::isfinite(w)) die("fir-dirs weight is not finite: " + line);
+                    p.pairs.push_back({(int)ix, w});
+                }
+                if (p.pairs.empty() || p.pairs.size() > 8) die("fir-dirs line needs 1 .. 8 pairs of <index> <weight>: " + line);
+                scene.bank_J = std::max(scene.bank_J, (int)p.pairs.size());
+            } else if (!(iss >> p.b >> p.copy >> p.onset >> path)) die("bad fir line (<buffer> <copy> <onset> <taps file>): " + line);
             if (p.copy < 0 || p.copy >= scene.copies) die("fir line for a copy that does not exist: " + line);
             if (p.b < 0 || p.b >= n_buffers) die("fir line outside buffers 0 .. --buffers - 1: " + line);
             if (p.onset < 0 || p.onset > (1 << 20)) die("fir onset outside [0, 1048576]: " + line);
-            p.file = (int)(std::find(paths.begin(), paths.end(), path) - paths.begin());
-            if (p.file == (int)paths.size()) {               // a path not seen yet: loaded once
+            p.file = scene.fir_bank ? -1 : (int)(std::find(paths.begin(), paths.end(), path) - paths.begin());
+            if (!scene.fir_bank && p.file == (int)paths.size()) {   // a path not seen yet: loaded once
                 paths.push_back(path);
                 std::ifstream tf(path, std::ios::binary);
                 if (!tf) die("cannot read taps file " + path);
@@ -830,6 +901,8 @@ int main(int argc, char **argv) {
             scene.fir_lines.push_back(p);
         }
         if (scene.fir_lines.empty()) die("no lines in " + fir);
+        scene.bank_index.assign((size_t)scene.copies * scene.bank_J, 0);
+        scene.bank_weight.assign((size_t)scene.copies * scene.bank_J, 0.f);
         if (!fir_delay.empty()) {
             // the delay stage's script: <buffer> <copy> <delay in samples>; max_delay is the largest value, rounded up
             if (scene.fir_delay_ramp < 0 || scene.fir_delay_ramp > (1 << 20)) die("--delay-ramp must be 0 .. 1048576");
@@ -985,6 +1058,7 @@ int main(int argc, char **argv) {
             const size_t total = (size_t)n_run * PBSO_FRAMES_PER_BUFFER;
             if (scene.fir) check(e, pbso_scene_fir_enable(e, C, scene.n_taps, scene.max_onset, scene.xfade), "scene_fir_enable");
             else check(e, pbso_scene_mix_enable(e, C, scene.max_delay, scene.ramp), "scene_mix_enable");
+            if (scene.fir_bank) check(e, pbso_scene_fir_bank_create(e, scene.bank_F, scene.bank.data()), "scene_fir_bank_create");
             if (!scene.fir_delay_lines.empty())
                 check(e, pbso_scene_fir_delay_enable(e, scene.fir_max_delay, scene.fir_delay_ramp), "scene_fir_delay_enable");
             std::vector<float> delay_now(1, 0.f);
@@ -1007,7 +1081,12 @@ int main(int argc, char **argv) {
                 });
             if (scene.fir_schedule)
                 scene.schedule_fir(taps, onset, delay_now,
-                                   [&](int64_t t, const float *h, const int *on) { check(e, pbso_scene_fir_set_at(e, t, h, on), "scene_fir_set_at"); },
+                                   [&](int64_t t, const float *h, const int *on) {
+                                       if (scene.fir_bank)
+                                           check(e, pbso_scene_fir_set_bank_at(e, t, scene.bank_J, scene.bank_index.data(), scene.bank_weight.data(), on),
+                                                 "scene_fir_set_bank_at");
+                                       else check(e, pbso_scene_fir_set_at(e, t, h, on), "scene_fir_set_at");
+                                   },
                                    [&](int64_t t, const float *dl) { check(e, pbso_scene_fir_set_delay_at(e, t, dl), "scene_fir_set_delay_at"); });
             std::vector<int> cuts = retune.cut(scene.cuts(n_buffers), n_buffers);
             if (n_tail) cuts.push_back(n_run);
@@ -1018,7 +1097,12 @@ int main(int argc, char **argv) {
                 } else if (scene.fir_schedule) {
                     // (scheduled up front)
                 } else if (scene.fir) {
-                    if (scene.fir_set_at(cuts[k], taps, onset)) check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
+                    if (scene.fir_set_at(cuts[k], taps, onset)) {
+                        if (scene.fir_bank)
+                            check(e, pbso_scene_fir_set_bank(e, scene.bank_J, scene.bank_index.data(), scene.bank_weight.data(), onset.data()),
+                                  "scene_fir_set_bank");
+                        else check(e, pbso_scene_fir_set(e, taps.data(), onset.data()), "scene_fir_set");
+                    }
                     if (scene.fir_delay_set_at(cuts[k], delay_now)) check(e, pbso_scene_fir_set_delay(e, delay_now.data()), "scene_fir_set_delay");
                 } else if (scene.pan_schedule) {
                     // (scheduled up front)
