@@ -838,6 +838,75 @@ int pbso_resample_reset(pbso_engine *e);
  * over 2 L in input samples, over 2 M in output samples), out[7] = n_out of the last call */
 int pbso_resample_info(pbso_engine *e, int64_t out[8]);
 
+/* EQ bus: biquad cascades -- S second-order IIR sections in cascade on every channel of a device buffer [C][n] (what the mixers,
+ * the reverb and the master bus read and write): a high-pass in front of the limiter, a shelf on the reverb send, peaking bands on
+ * the master.  The recurrence is evaluated in block form, so that a step of any length is parallel work, bit-reproducible and
+ * independent of how the samples are cut into steps.
+ * Why fp64 inside: an f32 biquad, serial or in block form, is 1e-4 to 2e-3 of peak away from the fp64 recurrence for sections at
+ * 20 .. 100 Hz (coefficient rounding at a1 near -2).  So inputs and outputs are f32 and everything between is fp64: tables, states
+ * and the signals between sections; the result is rounded to f32 once at the end.
+ * Stage: C channels, 1 .. 8; S sections per channel, 1 .. 8, in cascade.  Section (c, s) has five fp64 coefficients b0 b1 b2 a1 a2
+ * (a0 = 1).  Signal 0 of channel c is (double)u_c(t); signal s + 1 is the output of section s.  All signals are 0 for t < 0.
+ * t counts processed samples from the enable or the last reset, 64-bit.
+ * Block form: P = PBSO_EQ_BLOCK is part of the definition.  A coefficient set in force since absolute sample t_set has its block
+ * origins at T0 = t_set + g * P.  For a section with input x and output y, five tables of P doubles are built on the host at the set
+ * call by running the recurrence  o = b0 v + b1 x1 + b2 x2 - a1 y1 - a2 y2  in fp64, in this literal order of operations (no fused
+ * multiply-add), over P samples: h, the response to a unit impulse from zero state; r, s, p, q, the response with zero input to unit
+ * x(T0-1), x(T0-2), y(T0-1), y(T0-2) respectively.  Order of arithmetic, with fma the fp64 fused multiply-add:
+ *     y(T0+k): acc = 0.0; for j = k down to 0: acc = fma(h[j], x(T0+k-j), acc);
+ *              acc = fma(r[k], x(T0-1), acc); acc = fma(s[k], x(T0-2), acc);
+ *              acc = fma(q[k], y(T0-2), acc); acc = fma(p[k], y(T0-1), acc)
+ * one fp64 chain per sample, nothing split over accumulators; the only serial dependence across blocks is two fma per block and
+ * section.  out_c(t) = (float)signal S.  Subnormals are kept.  A non-finite input leaves every later output of that channel
+ * unspecified.  Against the serial fp64 recurrence the block form stays within 1e-9 of peak (DESIGN.md has the table).
+ * Sets and the cross-fade: enable and reset install the identity cascade (b0 = 1, the rest 0, t_set = 0), under which the output is
+ * the input bit for bit.  A set (pbso_eq_set: sos [C][S][5]) takes effect at t_set = the first sample of the next processed step.
+ * With xfade_samples R > 0 the old cascade (From) keeps running on its own grid through t_set + R - 2 and the new one (To) starts
+ * at t_set on a grid of its own; for t < t_set To takes every signal's values from From (the direct-form-I state, so nothing
+ * jumps).  While t - t_set + 1 < R:  out = yf + w * (yt - yf)  with yf = (float)From, yt = (float)To and
+ * w = (float)((double)(t - t_set + 1) / (double)R), three separately rounded f32 operations; after that only To.  R = 0: To at
+ * once.  The first set after enable or reset fades from the identity like any other.  A set with no step since the previous set
+ * replaces it.  A set while a fade runs is PBSO_ERR_STATE.  Validation happens before anything changes: all values finite, every
+ * section stable (|a2| < 1 and |a1| < 1 + a2), else PBSO_ERR_INVALID and the stage stays as it was.
+ * State: for each cascade (at most two), channel and signal, the device keeps the last P + 2 fp64 samples, double-buffered as the
+ * master bus's history.  A step may end inside a block; the next step finishes that block from the same origin, so each sample is
+ * computed by the formula above whatever the cut.
+ * pbso_eq processes n = the last step's n_buffers * frames_per_buffer samples: d_in [C][n] f32 on the device, required; d_out [C][n]
+ * or NULL for an engine-owned buffer; d_out == d_in is allowed (the input is read before anything is written), any other overlap is
+ * PBSO_ERR_INVALID.  Asynchronous on the engine's stream.  While enabled, every step is processed exactly once: a second call for the
+ * same step, a call after a step that was skipped or a call before any step is PBSO_ERR_STATE.  A refused call changes nothing.  The
+ * stage knows nothing of the other buses.  A device group has none.
+ * pbso_eq_tables reads back the tables in force, [C][S][5][P] in the order h r s p q: To's, once its set has taken effect.
+ * pbso_eq_design needs no engine: the Audio-EQ-Cookbook forms, computed in fp64 exactly as written here.  With
+ *     w0 = 2 pi f0 / rate, cs = cos(w0), sn = sin(w0), alpha = sn / (2 Q), A = pow(10, gain_db / 40), g = 2 sqrt(A) alpha
+ *   low-pass    b1 = 1 - cs, b0 = b2 = b1 / 2;            a0 = 1 + alpha, a1 = -2 cs, a2 = 1 - alpha
+ *   high-pass   b1 = -(1 + cs), b0 = b2 = (1 + cs) / 2;   a0, a1, a2 as the low-pass
+ *   peaking     b0 = 1 + alpha A, b1 = -2 cs, b2 = 1 - alpha A;   a0 = 1 + alpha / A, a1 = -2 cs, a2 = 1 - alpha / A
+ *   low shelf   b0 = A ((A+1) - (A-1) cs + g), b1 = 2 A ((A-1) - (A+1) cs), b2 = A ((A+1) - (A-1) cs - g);
+ *               a0 = (A+1) + (A-1) cs + g, a1 = -2 ((A-1) + (A+1) cs), a2 = (A+1) + (A-1) cs - g
+ *   high shelf  b0 = A ((A+1) + (A-1) cs + g), b1 = -2 A ((A-1) + (A+1) cs), b2 = A ((A+1) + (A-1) cs - g);
+ *               a0 = (A+1) - (A-1) cs + g, a1 = 2 ((A-1) - (A+1) cs), a2 = (A+1) - (A-1) cs - g
+ * out = b0/a0 b1/a0 b2/a0 a1/a0 a2/a0.  rate > 0, 0 < f0 < rate / 2, Q > 0, |gain_db| <= 120, all finite, else PBSO_ERR_INVALID;
+ * gain_db is read by the peaking and shelf forms only.                                                                             */
+#define PBSO_EQ_BLOCK 64
+enum pbso_eq_kind {
+    PBSO_EQ_LOWPASS = 0,
+    PBSO_EQ_HIGHPASS = 1,
+    PBSO_EQ_PEAK = 2,
+    PBSO_EQ_LOWSHELF = 3,
+    PBSO_EQ_HIGHSHELF = 4
+};
+int pbso_eq_enable(pbso_engine *e, int n_channels, int n_sections, int xfade_samples);   /* after finalize; xfade_samples 0 .. 1 << 20 */
+int pbso_eq_set(pbso_engine *e, const double *sos);                          /* [C][S][5] = b0 b1 b2 a1 a2 */
+int pbso_eq(pbso_engine *e, const void *d_in, void *d_out);                  /* n = last step's n_buffers * 513; [C][n] f32; d_out NULL = engine-owned; d_out == d_in allowed */
+int pbso_read_eq(pbso_engine *e, float *host_out, size_t n);                 /* planar [C][n], synchronous; n = C * n_buffers * 513 */
+int pbso_eq_tables(pbso_engine *e, double *out, size_t n);                   /* [C][S][5][P]; n = C * S * 5 * PBSO_EQ_BLOCK */
+int pbso_eq_reset(pbso_engine *e);
+/* out[0] = t of the next processed sample, out[1] = the first t at which the running fade is over (= out[0] when none runs),
+ * out[2] = steps processed, out[3] = sets accepted */
+int pbso_eq_info(pbso_engine *e, int64_t out[4]);
+int pbso_eq_design(int kind, double rate, double f0, double q, double gain_db, double out[5]);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a

@@ -57,6 +57,8 @@ EXPORTS = [
     # the resampler bus (a bus [C][n] at sample_rate out at another rate: rational polyphase, meters and 16-bit PCM)
     "pbso_resample_enable", "pbso_resample", "pbso_resample_max_out", "pbso_read_resample", "pbso_read_resample_pcm16",
     "pbso_read_resample_meters", "pbso_resample_taps", "pbso_resample_reset", "pbso_resample_info",
+    # the EQ bus (biquad cascades per channel of a bus [C][n], block-parallel in fp64; the cookbook designs)
+    "pbso_eq_enable", "pbso_eq_set", "pbso_eq", "pbso_read_eq", "pbso_eq_tables", "pbso_eq_reset", "pbso_eq_info", "pbso_eq_design",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -311,6 +313,15 @@ def lib():
         l.pbso_resample_taps.argtypes = [vp, fp, C.c_size_t]
         l.pbso_resample_reset.argtypes = [vp]
         l.pbso_resample_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_eq"):
+        l.pbso_eq_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        l.pbso_eq_set.argtypes = [vp, dp]
+        l.pbso_eq.argtypes = [vp, vp, vp]
+        l.pbso_read_eq.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_eq_tables.argtypes = [vp, dp, C.c_size_t]
+        l.pbso_eq_reset.argtypes = [vp]
+        l.pbso_eq_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_eq_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_set_material"):
         l.pbso_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
         l.pbso_get_material.argtypes = [vp, C.c_int, C.POINTER(Material)]
@@ -346,3 +357,17 @@ def lib():
     l.pbso_group_read_result.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     _lib = l
     return l
+
+
+EQ_BLOCK = 64                                         # PBSO_EQ_BLOCK: part of the EQ bus's definition
+EQ_LOWPASS, EQ_HIGHPASS, EQ_PEAK, EQ_LOWSHELF, EQ_HIGHSHELF = 0, 1, 2, 3, 4
+EQ_KINDS = {"lowpass": EQ_LOWPASS, "highpass": EQ_HIGHPASS, "peak": EQ_PEAK, "lowshelf": EQ_LOWSHELF, "highshelf": EQ_HIGHSHELF}
+
+
+def eq_design(kind, rate, f0, q=0.7071067811865476, gain_db=0.0):
+    """pbso_eq_design: one Audio-EQ-Cookbook section, b0 b1 b2 a1 a2 (a0 = 1) as five doubles; kind: a name of EQ_KINDS or its number"""
+    out = (C.c_double * 5)()
+    rc = lib().pbso_eq_design(EQ_KINDS[kind] if isinstance(kind, str) else int(kind), rate, f0, q, gain_db, out)
+    if rc != 0:
+        raise ValueError(f"pbso_eq_design({kind!r}, {rate}, {f0}, {q}, {gain_db}): status {rc}")
+    return [float(v) for v in out]

@@ -845,6 +845,62 @@ int pbso_resample_info(pbso_engine *e, int64_t out[8]) {
     GUARD_END(e)
 }
 
+int pbso_eq_enable(pbso_engine *e, int n_channels, int n_sections, int xfade_samples) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->eq_enable(n_channels, n_sections, xfade_samples);
+    GUARD_END(e)
+}
+
+int pbso_eq_set(pbso_engine *e, const double *sos) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->eq_set(sos);
+    GUARD_END(e)
+}
+
+int pbso_eq(pbso_engine *e, const void *d_in, void *d_out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->eq(d_in, d_out);
+    GUARD_END(e)
+}
+
+int pbso_read_eq(pbso_engine *e, float *host_out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_eq(host_out, n);
+    GUARD_END(e)
+}
+
+int pbso_eq_tables(pbso_engine *e, double *out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_tables(out, n);
+    GUARD_END(e)
+}
+
+int pbso_eq_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->eq_reset();
+    GUARD_END(e)
+}
+
+int pbso_eq_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_info(out);
+    GUARD_END(e)
+}
+
+// (pbso_eq_design is in eq.cpp: its arithmetic is compiled without FMA contraction)
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

@@ -30,6 +30,7 @@ struct SceneFir;         // scene_fir.cpp
 struct SceneReverb;      // scene_reverb.cpp
 struct Master;           // master.cpp
 struct Resample;         // resample.cpp
+struct Eq;               // eq.cpp
 struct TrackPool;        // track_pool.cpp
 struct BusOut;           // bus_state.h
 struct BusWords;         // bus_clock.h
@@ -316,6 +317,14 @@ public:
     int resample_taps(float *out, size_t n);
     int resample_reset();
     int resample_info(int64_t out[8]);
+    // the EQ bus (eq.cpp, kernels_eq.hip): biquad cascades per channel of a caller's bus [C][n], block-parallel in fp64
+    int eq_enable(int n_channels, int n_sections, int xfade_samples);
+    int eq_set(const double *sos);
+    int eq(const void *d_in, void *d_out);
+    int read_eq(float *out, size_t n);
+    int eq_tables(double *out, size_t n);
+    int eq_reset();
+    int eq_info(int64_t out[4]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -591,6 +600,8 @@ private:
     void master_release();
     Resample *resample_ = nullptr;                       // pbso_resample_enable
     void resample_release();
+    Eq *eq_ = nullptr;                                   // pbso_eq_enable
+    void eq_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

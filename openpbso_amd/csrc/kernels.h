@@ -460,6 +460,18 @@ int launch_resample(const float *in, int C, long long n, const float *hist, floa
 // pcm [n][C] = (int16_t)lrintf(clamp(y[c][s], -1.f, 1.f) * 32767.f) of y [C][stride]
 int launch_resample_pcm16(const float *y, int C, long long n, long long stride, short *pcm, hipStream_t stream);
 
+// pbso_eq (kernels_eq.hip): one cascade of the EQ bus on the first n samples of in's C rows (in_stride apart) in fp64 block form (eq_block.h: EQ_BLOCK, EQ_HIST).  k0 = where the
+// step's first sample lies in its block; hist / hist_next [C][S + 1][EQ_HIST] the samples of every signal before / behind the
+// step; tab [C][S][5][EQ_BLOCK]; work: eq_work_doubles(C, n) doubles.  *result = signal S as rows of EQ_HIST + n doubles, the
+// step's samples from index EQ_HIST on, inside work.
+size_t eq_work_doubles(int C, long long n);
+int launch_eq_cascade(const float *in, long long in_stride, int C, int S, long long n, int k0, const double *hist, double *hist_next, const double *tab,
+                      double *work, const double **result, hipStream_t stream);
+// out[c][i] = (float)to_c(i), i < n; for i < n_fade (then R >= 2 and from, rows of EQ_HIST + n_fade, is read): yf + w (yt - yf),
+// w = (float)((double)(d0 + i) / (double)R), d0 = t - t_set + 1.  out may be the cascades' input.
+int launch_eq_output(const double *to, const double *from, int C, long long n, long long n_fade, long long d0, int R, float *out,
+                     hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -930,6 +930,47 @@ class Engine:
         self._chk(self._l.pbso_resample_info(self._h, v))
         return {"t": v[0], "m": v[1], "calls": v[2], "L": v[3], "M": v[4], "T": v[5], "delay_num": v[6], "n_out": v[7]}
 
+    # -- EQ bus: biquad cascades per channel of a device buffer [C][n], block-parallel in fp64, state kept across steps -----------
+    def eq_enable(self, n_channels, n_sections, xfade_samples=0):
+        """pbso_eq_enable: the identity cascade; from the next step on, every step is processed exactly once (eq)"""
+        self._chk(self._l.pbso_eq_enable(self._h, n_channels, n_sections, xfade_samples))
+        self._eq_shape, self._eq_nb = (n_channels, n_sections), 0
+
+    def eq_set(self, sos):
+        """pbso_eq_set: sos [C][S][5] = b0 b1 b2 a1 a2 in fp64; takes effect at the first sample of the next processed step"""
+        c = np.ascontiguousarray(sos, dtype=np.float64)
+        if c.size != self._eq_shape[0] * self._eq_shape[1] * 5:
+            raise PbsoError(capi.ERR_INVALID, "eq_set: sos must be [n_channels][n_sections][5]")
+        self._chk(self._l.pbso_eq_set(self._h, c.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def eq(self, d_in, d_out=None):
+        """pbso_eq: the device buffer d_in [C][n_buffers * frames] f32 of the last step through the cascades into d_out (None: the
+        engine's own; may be d_in).  Device pointers as integers."""
+        vp = lambda p: None if p is None else C.c_void_p(p)
+        self._chk(self._l.pbso_eq(self._h, vp(d_in), vp(d_out)))
+        self._eq_nb = self._last_nb
+
+    def read_eq(self):
+        """the last EQ output: [C][n_buffers * frames] float32 (synchronous)"""
+        out = np.empty((self._eq_shape[0], self._eq_nb * self.B), dtype=np.float32)
+        self._chk(self._l.pbso_read_eq(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def eq_tables(self):
+        """the block tables in force: [C][S][5][PBSO_EQ_BLOCK] float64, in the order h r s p q"""
+        out = np.empty(self._eq_shape + (5, capi.EQ_BLOCK), dtype=np.float64)
+        self._chk(self._l.pbso_eq_tables(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+        return out
+
+    def eq_reset(self):
+        self._chk(self._l.pbso_eq_reset(self._h))
+
+    def eq_info(self):
+        """pbso_eq_info: t of the next processed sample, the first t at which the running fade is over, calls, sets"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_eq_info(self._h, v))
+        return {"t": v[0], "fade_end": v[1], "calls": v[2], "sets": v[3]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

@@ -78,6 +78,13 @@
 //                    the tool steps enough more buffers with no hits to flush d, drops the first floor(d L / M + 0.5) output
 //                    frames and writes ceil(buffers * 513 * L / M) of them.  --pcm16 beside it takes the resampler's saturating
 //                    PCM (pbso_read_resample_pcm16) and still needs --limit.  One engine only: not with --devices; not with --raw.
+//   --eq FILE [--eq-xfade N]   with --channels C and one of --pan / --fir: the EQ bus (pbso_eq) behind the mixers and the reverb and in
+//                    front of --limit and --out-rate, on the samples of the WAV without it.  Lines <buffer> <section> <kind> <f0>
+//                    <Q> <gain dB> give section 0 .. 7 of every channel the cookbook design (pbso_eq_design; kind lowpass, highpass,
+//                    peak, lowshelf or highshelf) from that buffer on; the sections not named yet pass the signal through.  The run
+//                    is cut at these buffers as --pan cuts it; a buffer's lines are one set, cross-faded over N samples (default
+//                    441; a fade must be over before the next set, else the run ends with the engine's refusal).  One engine only:
+//                    not with --devices; not with --raw.
 //   --retune FILE    materials changed during the run (pbso_set_material; with --devices pbso_group_set_material): lines
 //                    <buffer> <copy> <material file> [keep|zero] give copy the file's material (the format of -t) from that
 //                    buffer on; keep (the default): the state carries on under the new coefficients, zero: it is cleared.  Every
@@ -98,6 +105,7 @@
 
 #include "openpbso_amd.h"
 #include "resample_clock.h"                              // (openpbso_amd/csrc: the resampler's limits and counts, no HIP in it)
+#include "eq_block.h"                                    // (openpbso_amd/csrc: the EQ bus's limits and refusals, no HIP in it)
 
 static void die(const std::string &msg) {
     std::fprintf(stderr, "pbso_headless: %s\n", msg.c_str());
@@ -563,8 +571,58 @@ static int run_group(const std::vector<int> &devices, int copies, int shift, con
     return 0;
 }
 
+// --eq: the script's lines; the coefficients in force, [S][5], are those of every channel
+struct EqScript {
+    struct Line { long b; int section, kind; double f0, q, gain; };
+    std::vector<Line> lines;
+    int S = 0, xfade = 441;
+    bool on() const { return S > 0; }
+    void read(const std::string &path, int n_buffers) {
+        static const char *kinds[] = {"lowpass", "highpass", "peak", "lowshelf", "highshelf"};
+        std::ifstream f(path);
+        if (!f) die("cannot read " + path);
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream iss(line);
+            Line p;
+            std::string kind;
+            if (!(iss >> p.b >> p.section >> kind >> p.f0 >> p.q >> p.gain)) die("bad eq line (<buffer> <section> <kind> <f0> <Q> <gain dB>): " + line);
+            p.kind = -1;
+            for (int k = 0; k < 5; ++k)
+                if (kind == kinds[k]) p.kind = k;
+            if (p.kind < 0) die("eq kind must be lowpass, highpass, peak, lowshelf or highshelf: " + line);
+            if (p.b < 0 || p.b >= n_buffers) die("eq line outside buffers 0 .. --buffers - 1: " + line);
+            if (p.section < 0 || p.section >= pbso::EQ_MAX_SECTIONS) die("eq section must be 0 .. 7: " + line);
+            if (const char *why = pbso::eq_design_refusal(p.kind, (double)PBSO_SAMPLE_RATE, p.f0, p.q, p.gain)) die(std::string("eq line: ") + why + ": " + line);
+            S = std::max(S, p.section + 1);
+            lines.push_back(p);
+        }
+        if (lines.empty()) die("no lines in " + path);
+    }
+    std::vector<int> cut(std::vector<int> cuts, int n_buffers) const {
+        for (const Line &p : lines)
+            if (p.b > 0 && p.b < n_buffers) cuts.push_back((int)p.b);
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        return cuts;
+    }
+    // the lines of buffer b into sos [S][5]; false when it has none
+    bool set_at(long b, std::vector<double> &sos) const {
+        bool any = false;
+        for (const Line &p : lines)
+            if (p.b == b) {
+                if (pbso_eq_design(p.kind, (double)PBSO_SAMPLE_RATE, p.f0, p.q, p.gain, sos.data() + 5 * (size_t)p.section) != PBSO_OK) die("eq_design");
+                any = true;
+            }
+        return any;
+    }
+};
+
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_dirs, fir_bank, fir_delay, reverb, strokes_file, arprm_arg, retune_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_dirs, fir_bank, fir_delay, reverb, strokes_file, arprm_arg, retune_arg, eq_arg;
+    EqScript eq;
+    bool eq_flag = false;                                // --eq-xfade was given
     StrokeScript strokes;
     int n_buffers = 86, copies = 0, copy_shift = 1, time_chunks = 0;
     Scene scene;
@@ -625,7 +683,18 @@ int main(int argc, char **argv) {
         else if (a == "--rs-taps") { rs_flag = true; rs_taps = std::atoi(val().c_str()); }
         else if (a == "--rs-beta") { rs_flag = true; rs_beta = std::atof(val().c_str()); }
         else if (a == "--rs-cutoff") { rs_flag = true; rs_cutoff = std::atof(val().c_str()); }
+        else if (a == "--eq") eq_arg = val();
+        else if (a == "--eq-xfade") { eq_flag = true; eq.xfade = std::atoi(val().c_str()); }
         else die("unknown flag " + a);
+    }
+    if (eq_flag && eq_arg.empty()) die("--eq-xfade belongs to --eq FILE");
+    if (!eq_arg.empty()) {
+        if (!devices_arg.empty()) die("--eq runs on one engine, not through a device group (--devices)");
+        if (!raw.empty()) die("--raw dumps the unscaled mix: not with --eq");
+        if (scene.channels < 1 || scene.channels > 8 || (pan.empty() && fir.empty() && fir_dirs.empty()))
+            die("--eq needs --channels C (1 .. 8) and one of --pan FILE or --fir FILE: it filters that mix");
+        if (eq.xfade < 0 || eq.xfade > (1 << 20)) die("--eq-xfade must be 0 .. 1048576");
+        eq.read(eq_arg, n_buffers);
     }
     if (pcm16 && !limit) die("--pcm16 needs --limit T: an integer WAV clips without a ceiling");
     if (master_flag && !limit) die("--lookahead, --hold and --gain belong to --limit T");
@@ -1009,7 +1078,7 @@ int main(int argc, char **argv) {
             while (pbso::resample_max_out((long long)(n_buffers + n_tail) * PBSO_FRAMES_PER_BUFFER, rs_L, rs_M) < rs_drop + rs_keep) ++n_tail;
         }
         const int n_run = n_buffers + n_tail;
-        const bool post = limit || out_rate;                 // the segments go through a bus behind the mix
+        const bool post = limit || out_rate || eq.on();      // the segments go through a bus behind the mix
         void *m_in = nullptr;
         if (post && pbso_host_alloc((size_t)channels_out * n_run * PBSO_FRAMES_PER_BUFFER * sizeof(float), &m_in) != PBSO_OK)
             die("cannot allocate the master bus's input");
@@ -1021,9 +1090,28 @@ int main(int argc, char **argv) {
             check(e, pbso_resample_enable(e, channels_out, out_rate, rs_taps, rs_beta, rs_cutoff), "resample_enable");
             resampled.resize(channels_out);
         }
+        std::vector<double> eq_sos;                          // --eq: [C][S][5], every channel alike
+        if (eq.on()) {
+            check(e, pbso_eq_enable(e, channels_out, eq.S, eq.xfade), "eq_enable");
+            eq_sos.assign((size_t)channels_out * eq.S * 5, 0.0);
+            for (size_t i = 0; i < eq_sos.size(); i += 5) eq_sos[i] = 1.0;
+        }
+        // --eq: the lines of buffer b, given to every channel, before the step that begins there
+        auto eq_set_at = [&](int b) {
+            std::vector<double> one(eq_sos.begin(), eq_sos.begin() + (size_t)eq.S * 5);
+            if (!eq.on() || !eq.set_at(b, one)) return;
+            for (int c = 0; c < channels_out; ++c) std::copy(one.begin(), one.end(), eq_sos.begin() + (size_t)c * eq.S * 5);
+            check(e, pbso_eq_set(e, eq_sos.data()), "eq_set");
+        };
         auto master_segment = [&](std::vector<float> &seg) {         // seg [C][row], the last step's
             float *in = (float *)m_in;
             for (size_t i = 0; i < seg.size(); ++i) in[i] = (float)((double)seg[i] / 1E10);
+            // --eq in place, in front of the limiter and the resampler
+            if (eq.on()) check(e, pbso_eq(e, m_in, m_in), "eq");
+            if (!limit && !out_rate) {
+                check(e, pbso_read_eq(e, seg.data(), seg.size()), "read_eq");
+                return;
+            }
             if (out_rate) {
                 // the limiter in place (its input is read before anything is written), the resampler behind it from the same buffer
                 if (limit) check(e, pbso_master(e, m_in, m_in), "master");
@@ -1088,10 +1176,11 @@ int main(int argc, char **argv) {
                                        else check(e, pbso_scene_fir_set_at(e, t, h, on), "scene_fir_set_at");
                                    },
                                    [&](int64_t t, const float *dl) { check(e, pbso_scene_fir_set_delay_at(e, t, dl), "scene_fir_set_delay_at"); });
-            std::vector<int> cuts = retune.cut(scene.cuts(n_buffers), n_buffers);
+            std::vector<int> cuts = eq.cut(retune.cut(scene.cuts(n_buffers), n_buffers), n_buffers);
             if (n_tail) cuts.push_back(n_run);
             for (size_t k = 0; k + 1 < cuts.size(); ++k) {
                 if (cuts[k] < n_buffers) retune.apply_at(cuts[k], engine_set);
+                if (cuts[k] < n_buffers) eq_set_at(cuts[k]);
                 if (cuts[k] >= n_buffers) {
                     // (--limit's tail: the script ended with the run)
                 } else if (scene.fir_schedule) {
@@ -1178,6 +1267,17 @@ int main(int argc, char **argv) {
         }
         std::printf("%d buffers (%.3f s of audio) in %.3f ms on the device, %d Hz -> %s\n", n_buffers,
                     n_buffers * (double)PBSO_FRAMES_PER_BUFFER / PBSO_SAMPLE_RATE, device_ms, out_rate, out.c_str());
+        return 0;
+    }
+    if (eq.on() && !limit) {
+        // the EQ bus's output is in the WAV's scale already, and not late
+        const size_t frames = sound.size() / channels;
+        std::vector<float> wav(sound.size());
+        for (size_t i = 0; i < frames; ++i)
+            for (int c = 0; c < channels; ++c) wav[i * channels + c] = sound[(size_t)c * frames + i];
+        write_wav_f32(out, wav, PBSO_SAMPLE_RATE, channels);
+        std::printf("%d buffers (%.3f s of audio) in %.3f ms on the device, equalised -> %s\n", n_buffers,
+                    n_buffers * (double)PBSO_FRAMES_PER_BUFFER / PBSO_SAMPLE_RATE, device_ms, out.c_str());
         return 0;
     }
     if (limit) {
