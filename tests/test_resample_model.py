@@ -15,32 +15,42 @@ from tests import resample_model as rm
 
 U24 = 2.0 ** -24
 RATIOS = [(44100, 48000), (44100, 96000), (44100, 22050), (48000, 44100), (44100, 44100), (3, 2)]
+# what tests/test_gpu_resample_windows.py leans on the reference for, (rates, taps, input samples): 2 / 95, 85 / 4079 and 84 / 4031 on
+# both sides of the kernel's window limit, 30000 samples of them (about 630 outputs; 1500 samples would give 32), and 8 / 7 and 1 / 7
+WINDOW_CASES = [((45600, 960), (172, 175, 176, 177), 30000), ((44869, 935), (50, 51, 52), 30000), ((44341, 924), (51, 52), 30000),
+                ((44100, 50400), (4, 7), 1500), ((44100, 6300), (4, 7), 1500)]
 
 
 def _signal(C, n, seed):
     return np.random.default_rng(seed).uniform(-1.0, 1.0, (C, n)).astype(np.float32)
 
 
-@pytest.mark.parametrize("rates", RATIOS)
-@pytest.mark.parametrize("T", [1, 2, 7, 32, 256])
-def test_f32_chain_within_its_bound_of_the_fp64_evaluation(rates, T):
+def _cases(taps):
+    """(rates, T, n): RATIOS x taps at 1500 samples, under the ids that two stacked parametrisations gave them, then WINDOW_CASES"""
+    old = [pytest.param(r, T, 1500, id=f"{T}-rates{i}") for T in taps for i, r in enumerate(RATIOS)]
+    return old + [pytest.param(r, T, n, id=f"{T}-{r[0]}to{r[1]}") for r, ts, n in WINDOW_CASES for T in ts]
+
+
+@pytest.mark.parametrize("rates,T,n", _cases([1, 2, 7, 32, 256]))
+def test_f32_chain_within_its_bound_of_the_fp64_evaluation(rates, T, n):
     L, M = rm.ratio(*rates)
     h = rm.design(L, M, T)
-    u = _signal(2, 1500, 7 * T + L)
+    u = _signal(2, n, 7 * T + L)
     y = rm.Model(2, L, M, h).process(u)
     y64, bound = rm.evaluate64(u, L, M, h)
-    assert y.shape == y64.shape == (2, rm.ceil_div(1500 * L, M))
+    assert y.shape == y64.shape == (2, rm.ceil_div(n * L, M))
     err = np.abs(y.astype(np.float64) - y64)
     assert (err <= (T + 1) * U24 * bound).all(), (err / bound).max() / U24
     assert np.abs(y).max() > 1e-4                        # (not silence; the window of a one- or two-tap table is nearly shut)
 
 
-@pytest.mark.parametrize("rates", RATIOS)
-@pytest.mark.parametrize("T", [1, 7, 32, 256])
-def test_cut_into_steps_equals_one_piece_bit_for_bit(rates, T):
+@pytest.mark.parametrize("rates,T,n", _cases([1, 7, 32, 256]))
+def test_cut_into_steps_equals_one_piece_bit_for_bit(rates, T, n):
     L, M = rm.ratio(*rates)
     h = rm.design(L, M, T)
     cuts = [1, 1, 3, 513, 2, 27, 1026, 5, 40]            # steps shorter than the history among them
+    if n > 1500:
+        cuts = cuts + [12312, 27, 1, 513, 15503, 26]     # at 47 : 1, two steps of more than 256 outputs among steps of 0 or 1
     n = sum(cuts)
     u = _signal(3, n, T + M)
     whole = rm.Model(3, L, M, h).process(u)
