@@ -1,6 +1,8 @@
-"""The reference of the master bus's tests: tests/cpp/master_ref.c (the stated order of arithmetic in about 30 lines of C) compiled
-with the host compiler into a temporary directory, and a model around it that keeps the history of v, the gain with its ramp and t
-as the engine does, and computes the meters of every buffer.  The window's taps are an input: no test depends on a cos."""
+"""The reference of the master bus's tests: tests/cpp/master_ref.c (the stated order of arithmetic in a page of C) compiled with the
+host compiler into a temporary directory, and a model around it that keeps the history of v, the gain with its ramp and t as the
+engine does, and computes the meters of every buffer.  The window's taps are an input: no test depends on a cos.  The C file has
+the sliding minimum twice: in linear time (master_ref, what every test runs against) and as the header's double loop
+(master_ref_literal: evaluate(..., literal=True), Model(..., literal=True)); tests/test_master_model.py holds the two bit-equal."""
 import ctypes as C
 import os
 import subprocess
@@ -25,8 +27,9 @@ def ref_lib():
                         os.path.join(_HERE, "cpp", "master_ref.c"), "-o", so, "-lm"], check=True)
         _lib = C.CDLL(so)
         fp = C.POINTER(C.c_float)
-        _lib.master_ref.argtypes = [fp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_float, fp, fp, fp, C.POINTER(C.c_long)]
-        _lib.master_ref.restype = None
+        for f in (_lib.master_ref, _lib.master_ref_literal):
+            f.argtypes = [fp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_float, fp, fp, fp, C.POINTER(C.c_long)]
+            f.restype = None
     return _lib
 
 
@@ -39,21 +42,24 @@ def window(L):
     return (h / s).astype(np.float32)
 
 
-def evaluate(v, L, H, T, w):
-    """v [C][2 L + H + n] float32: the history in front of the step -> y [C][n], g [n], number of chains that ended above 1.f"""
+def evaluate(v, L, H, T, w, literal=False):
+    """v [C][2 L + H + n] float32: the history in front of the step -> y [C][n], g [n], number of chains that ended above 1.f
+    (literal: the sliding minimum by the header's double loop, O(n (L + H)), instead of in linear time)"""
     fp = C.POINTER(C.c_float)
     v = np.ascontiguousarray(v, dtype=np.float32)
     w = np.ascontiguousarray(w, dtype=np.float32)
     assert w.shape == (L,)
     n = v.shape[1] - (2 * L + H)
     y, g, cnt = np.empty((v.shape[0], n), dtype=np.float32), np.empty(n, dtype=np.float32), C.c_long(0)
-    ref_lib().master_ref(v.ctypes.data_as(fp), v.shape[0], n, L, H, C.c_float(T), w.ctypes.data_as(fp), y.ctypes.data_as(fp),
-                         g.ctypes.data_as(fp), C.byref(cnt))
+    master_ref = ref_lib().master_ref_literal if literal else ref_lib().master_ref
+    master_ref(v.ctypes.data_as(fp), v.shape[0], n, L, H, C.c_float(T), w.ctypes.data_as(fp), y.ctypes.data_as(fp),
+               g.ctypes.data_as(fp), C.byref(cnt))
     return y, g, cnt.value
 
 
 class Model:
-    def __init__(self, n_channels, ceiling, lookahead, hold, ramp, w=None, frames=B):
+    def __init__(self, n_channels, ceiling, lookahead, hold, ramp, w=None, frames=B, literal=False):
+        self.literal = literal
         self.B = frames                                                    # the meters' buffer length
         self.C, self.T, self.L, self.H, self.R = n_channels, float(np.float32(ceiling)), lookahead, hold, ramp
         self.HL = 2 * lookahead + hold
@@ -91,7 +97,7 @@ class Model:
         p = self._p(self.t + np.arange(n)).astype(np.float32)
         v = p[None, :] * u                                                 # one rounded f32 multiplication
         vv = np.concatenate([self.tail, v], axis=1)
-        y, g, cnt = evaluate(vv, self.L, self.H, self.T, self.w)
+        y, g, cnt = evaluate(vv, self.L, self.H, self.T, self.w, self.literal)
         self.n_acc_above_one += cnt
         self.tail = np.ascontiguousarray(vv[:, vv.shape[1] - self.HL:])
         self.t += n

@@ -1,12 +1,15 @@
 """The reference of the master bus (tests/cpp/master_ref.c through tests/master_model.py) held to independent answers, without a
 GPU: a literal Python transcription of the header's lines with an exact rational fmaf on tiny shapes, the hard ceiling, the exact
-pass-through of unlimited stretches, independence of how the samples are cut into steps, the gain ramp and the window."""
+pass-through of unlimited stretches, independence of how the samples are cut into steps, the gain ramp and the window.  The C file
+takes the sliding minimum twice, in linear time and by the header's double loop; the transcription anchors the loop, and the two
+are held bit-equal at windows around every power of two up to 4097."""
 import math
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests import master_window_plan as wp
 from tests.master_model import B, Model, evaluate, pcm16, window
 
 
@@ -73,14 +76,35 @@ def test_python_fmaf_rounds_once():
 def test_model_equals_the_literal_transcription(L, H):
     rng = np.random.default_rng(10 * L + H)
     u = rng.standard_normal((2, 40)).astype(np.float32)
-    m = Model(2, 0.7, L, H, 7)
-    m.set_gain(1.5)                                                  # a ramp over the first 7 samples
-    p = m._p(np.arange(40)).astype(np.float32)
-    assert p[0] != p[3] and p[6] == p[39] == np.float32(1.5)
-    got = np.concatenate([m.process(u[:, :13]), m.process(u[:, 13:])], axis=1)
-    want = brute(u, p, L, H, 0.7, m.w)
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    for literal in (True, False):                                    # the header's double loop, and the linear-time minimum
+        m = Model(2, 0.7, L, H, 7, literal=literal)
+        m.set_gain(1.5)                                              # a ramp over the first 7 samples
+        p = m._p(np.arange(40)).astype(np.float32)
+        assert p[0] != p[3] and p[6] == p[39] == np.float32(1.5)
+        got = np.concatenate([m.process(u[:, :13]), m.process(u[:, 13:])], axis=1)
+        want = brute(u, p, L, H, 0.7, m.w)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), literal
     assert (want != np.concatenate([np.zeros((2, L), dtype=np.float32), p * u], axis=1)[:, :40]).any()   # (something was limited)
+
+
+@pytest.mark.parametrize("W", [2, 3, 4, 5, 1023, 1024, 1025, 2047, 2048, 4097])
+def test_the_linear_time_minimum_equals_the_literal_loop_bit_for_bit(W):
+    """y, g and the count of master_ref against master_ref_literal: L = 1 with H = W - 2 and H = 0 with L = W - 1, on dense noise
+    and on the staircase of tests/master_window_plan.py (n = W + 3 x 513 at least; a staircase that needs more keeps its length)"""
+    n = W + 3 * B
+    for L, H in ((1, W - 2), (W - 1, 0)):
+        case = dict(W=W, L=L, H=H, C=2, seed=W)
+        stairs, _ = wp.staircase(case)
+        if stairs.shape[1] < n:
+            pad = np.random.default_rng(W).standard_normal((2, n - stairs.shape[1])) * wp.NOISE
+            stairs = np.concatenate([stairs, pad.astype(np.float32)], axis=1)
+        for name, u in (("dense", wp.dense(case, n)), ("staircase", stairs)):
+            v = np.concatenate([np.zeros((2, 2 * L + H), dtype=np.float32), u], axis=1)
+            y, g, cnt = evaluate(v, L, H, 0.7, window(L))
+            yl, gl, cntl = evaluate(v, L, H, 0.7, window(L), literal=True)
+            assert np.array_equal(y.view(np.uint32), yl.view(np.uint32)), (name, L, H)
+            assert np.array_equal(g.view(np.uint32), gl.view(np.uint32)) and cnt == cntl, (name, L, H)
+            assert (g < 1).any() and np.unique(g).size > 4
 
 
 @pytest.mark.parametrize("L", [1, 64])
@@ -197,4 +221,6 @@ def test_pcm16_rounds_to_nearest_even_after_one_f32_product():
     p = pcm16(y)
     assert p.shape == (7, 1) and p.dtype == np.int16
     assert p[:4, 0].tolist() == [0, 32767, -32767, 22937] and p[6, 0] == 0
+    # the two ties: the f32 products are exactly 0.5 and 1.5, and ties go to the even neighbour
+    assert (y[0, 4:6] * np.float32(32767.0)).tolist() == [0.5, 1.5] and p[4:6, 0].tolist() == [0, 2]
     assert evaluate(np.zeros((1, 2 + 4), dtype=np.float32), 1, 0, 1.0, np.ones(1, dtype=np.float32))[0].shape == (1, 4)
