@@ -906,6 +906,42 @@ int pbso_eq_reset(pbso_engine *e);
  * out[2] = steps processed, out[3] = sets accepted */
 int pbso_eq_info(pbso_engine *e, int64_t out[4]);
 int pbso_eq_design(int kind, double rate, double f0, double q, double gain_db, double out[5]);
+/* The EQ bus's SCHEDULE: coefficient sets that take effect at absolute samples the caller gives, any number of them inside one step,
+ * so that a swept filter -- a high-pass that opens, a shelf that follows the reverb send, a band that follows a retune -- does not
+ * cut the run, and every stage in front of the EQ with it, at every change point.
+ * EFFECT.  A scheduled set does exactly what pbso_eq_set does, with t_set given by the caller instead of "the first sample of the
+ *   next processed step": the new cascade's block origins are t_set + g * P; for t < t_set every one of its signals is the value of
+ *   the cascade in force at t; From keeps running on its own grid through t_set + R - 2; the fade is the three f32 operations stated
+ *   above.  The output still depends on the input, the sets and the absolute samples at which they took effect only: a schedule
+ *   processed in one step equals, bit for bit, the same input cut at every t_set with pbso_eq_set before each piece, however the
+ *   samples are cut into steps.
+ * VALIDATION, ALL OR NOTHING.  t_set must be >= the next processed sample (out[0] of pbso_eq_schedule_info) and strictly greater
+ *   than the last pending set's (a plain set still waiting for the next step counts as pending at the next processed sample).  No
+ *   set while a fade runs: against its predecessor, pending or in force, a set needs t_set - t_prev + 1 >= R whenever R >= 2 (out[2]
+ *   is the smallest t_set that passes); the identity installed by enable or reset is a predecessor with t_set = 0, since the first
+ *   set fades from the identity like any other.  Coefficients are validated as pbso_eq_set validates them.  Otherwise
+ *   PBSO_ERR_INVALID.  pbso_eq_schedule validates all of its sets before it takes any: a refused call changes nothing.
+ *   PBSO_ERR_STATE before the enable.  n_sets == 0 is accepted.
+ * LIFETIME.  A set scheduled beyond the next step stays pending until the step that contains it.  At most 65 536 sets may be pending
+ *   (more: PBSO_ERR_INVALID).  At most 4096 sets may take effect inside one processed step: with more, pbso_eq returns
+ *   PBSO_ERR_INVALID and nothing has changed (step in shorter pieces, or clear the schedule).  If the device memory for a step's
+ *   tables (n_sets_in_step * C * S * 5 * P doubles) or work rows cannot be allocated, pbso_eq returns PBSO_ERR_NOMEM and nothing has
+ *   changed.  The pending list holds coefficients; a step builds the tables of the sets it takes on the device, by the recurrence
+ *   above in its literal order.  A step in which no scheduled set takes effect is launched exactly as without a schedule, even when a
+ *   fade that a scheduled set started in an earlier step is still running; a step with sets inside it takes a number of launches
+ *   that does not depend on how many they are.
+ * WITH pbso_eq_set.  While scheduled sets are pending pbso_eq_set returns PBSO_ERR_STATE; with none pending it behaves exactly as
+ *   without a schedule.  After a drained schedule it continues from what the schedule left, mid-fade included (refused until the
+ *   fade is over, as ever): as if every scheduled set had been a plain set between two steps cut at its sample.
+ * pbso_eq_clear_schedule drops the sets not yet in force.  pbso_eq_reset and a new pbso_eq_enable drop them too.
+ * pbso_eq_schedule_info: out[0] = t of the next processed sample, out[1] = scheduled sets pending, out[2] = the smallest t_set the
+ *   next scheduled set may have, out[3] = the number of sets that took effect inside the last processed step (a plain set that the
+ *   step took counts as one).  pbso_eq_info out[3] counts every set of a pbso_eq_schedule call; out[1] stays the first t at which the
+ *   running fade is over.  pbso_eq_tables returns the tables of the last set that has taken effect.                              */
+int pbso_eq_set_at(pbso_engine *e, int64_t t_set, const double *sos /* [C][S][5] */);
+int pbso_eq_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const double *sos /* [n_sets][C][S][5] */);
+int pbso_eq_clear_schedule(pbso_engine *e);             /* drops the sets not yet in force */
+int pbso_eq_schedule_info(pbso_engine *e, int64_t out[4]);
 
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so

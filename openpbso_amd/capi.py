@@ -59,6 +59,8 @@ EXPORTS = [
     "pbso_read_resample_meters", "pbso_resample_taps", "pbso_resample_reset", "pbso_resample_info",
     # the EQ bus (biquad cascades per channel of a bus [C][n], block-parallel in fp64; the cookbook designs)
     "pbso_eq_enable", "pbso_eq_set", "pbso_eq", "pbso_read_eq", "pbso_eq_tables", "pbso_eq_reset", "pbso_eq_info", "pbso_eq_design",
+    # ... and its schedule (sets at absolute samples, any number of them inside one step)
+    "pbso_eq_set_at", "pbso_eq_schedule", "pbso_eq_clear_schedule", "pbso_eq_schedule_info",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -322,6 +324,11 @@ def lib():
         l.pbso_eq_reset.argtypes = [vp]
         l.pbso_eq_info.argtypes = [vp, C.POINTER(C.c_int64)]
         l.pbso_eq_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_eq_schedule"):
+        l.pbso_eq_set_at.argtypes = [vp, C.c_int64, dp]
+        l.pbso_eq_schedule.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp]
+        l.pbso_eq_clear_schedule.argtypes = [vp]
+        l.pbso_eq_schedule_info.argtypes = [vp, C.POINTER(C.c_int64)]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_set_material"):
         l.pbso_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
         l.pbso_get_material.argtypes = [vp, C.c_int, C.POINTER(Material)]

@@ -899,6 +899,34 @@ int pbso_eq_info(pbso_engine *e, int64_t out[4]) {
     GUARD_END(e)
 }
 
+int pbso_eq_set_at(pbso_engine *e, int64_t t_set, const double *sos) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_schedule("eq_set_at", 1, &t_set, sos);
+    GUARD_END(e)
+}
+
+int pbso_eq_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const double *sos) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_schedule("eq_schedule", n_sets, t_set, sos);
+    GUARD_END(e)
+}
+
+int pbso_eq_clear_schedule(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_clear_schedule();
+    GUARD_END(e)
+}
+
+int pbso_eq_schedule_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->eq_schedule_info(out);
+    GUARD_END(e)
+}
+
 // (pbso_eq_design is in eq.cpp: its arithmetic is compiled without FMA contraction)
 
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {

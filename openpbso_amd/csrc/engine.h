@@ -320,6 +320,9 @@ public:
     // the EQ bus (eq.cpp, kernels_eq.hip): biquad cascades per channel of a caller's bus [C][n], block-parallel in fp64
     int eq_enable(int n_channels, int n_sections, int xfade_samples);
     int eq_set(const double *sos);
+    int eq_schedule(const char *name, int n_sets, const int64_t *t_set, const double *sos);
+    int eq_clear_schedule();
+    int eq_schedule_info(int64_t out[4]);
     int eq(const void *d_in, void *d_out);
     int read_eq(float *out, size_t n);
     int eq_tables(double *out, size_t n);
@@ -602,6 +605,7 @@ private:
     void resample_release();
     Eq *eq_ = nullptr;                                   // pbso_eq_enable
     void eq_release();
+    int eq_scheduled(const void *d_in, void *d_out);     // a step with scheduled sets inside it
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

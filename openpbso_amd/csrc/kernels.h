@@ -472,6 +472,18 @@ int launch_eq_cascade(const float *in, long long in_stride, int C, int S, long l
 int launch_eq_output(const double *to, const double *from, int C, long long n, long long n_fade, long long d0, int R, float *out,
                      hipStream_t stream);
 
+// The EQ bus's schedule (kernels_eq_schedule.hip; eq_schedule.h has the plan and its records): pool [n_sections / (C S)][C][S][5][EQ_BLOCK]
+// from the coefficients sos [n_sections][5] on the device, by the recurrence of eq_block.h in its literal order.
+int launch_eq_sched_tables(const double *sos, long long n_sections, double *pool, hipStream_t stream);
+// One step with K >= 1 sets inside it: seg (2 + K EqSeg), vblk and fblk (EqBlk) on the device; tab2 the stage's two table slots,
+// pool the step's; hist_* / next_* [C][S + 1][EQ_HIST] of the set in force and of the one fading out, before and behind the step
+// (next_from is written when from_hist says so); work: eq_sched_work_doubles(C, n) doubles.  out [C][n] may be in.  The number of
+// launches is 2 + 3 S whatever K.
+size_t eq_sched_work_doubles(int C, long long n);
+int launch_eq_scheduled(const float *in, int C, int S, long long n, int R, const void *seg, int K, const void *vblk, int n_vblk, const void *fblk,
+                        int n_fblk, const double *tab2, const double *pool, const double *hist_to, const double *hist_from, double *next_to,
+                        double *next_from, int from_hist, int vs_last, double *work, float *out, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

@@ -943,6 +943,31 @@ class Engine:
             raise PbsoError(capi.ERR_INVALID, "eq_set: sos must be [n_channels][n_sections][5]")
         self._chk(self._l.pbso_eq_set(self._h, c.ctypes.data_as(C.POINTER(C.c_double))))
 
+    def eq_set_at(self, t_set, sos):
+        """pbso_eq_set_at: as eq_set, taking effect at the absolute sample t_set (inside a step or not)"""
+        self.eq_schedule([int(t_set)], np.ascontiguousarray(sos, dtype=np.float64)[None], _one=True)
+
+    def eq_schedule(self, t_set, sos, _one=False):
+        """pbso_eq_schedule: t_set [n_sets] ascending absolute samples, sos [n_sets][C][S][5].  All or nothing."""
+        t = np.ascontiguousarray(t_set, dtype=np.int64)
+        c = np.ascontiguousarray(sos, dtype=np.float64)
+        shape = getattr(self, "_eq_shape", None)                     # (not enabled yet: the call itself says so)
+        if shape is not None and c.size != t.size * shape[0] * shape[1] * 5:
+            raise PbsoError(capi.ERR_INVALID, "eq_schedule: sos must be [n_sets][n_channels][n_sections][5]")
+        tp, dp = t.ctypes.data_as(C.POINTER(C.c_int64)), c.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self._l.pbso_eq_set_at(self._h, int(t[0]), dp) if _one else self._l.pbso_eq_schedule(self._h, t.size, tp, dp))
+
+    def eq_clear_schedule(self):
+        """pbso_eq_clear_schedule: drops the scheduled sets not yet in force"""
+        self._chk(self._l.pbso_eq_clear_schedule(self._h))
+
+    def eq_schedule_info(self):
+        """pbso_eq_schedule_info: t of the next processed sample, scheduled sets pending, the smallest t_set the next scheduled set may
+        have, the sets that took effect inside the last processed step"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_eq_schedule_info(self._h, v))
+        return {"t": v[0], "pending": v[1], "next_t_min": v[2], "sets_in_step": v[3]}
+
     def eq(self, d_in, d_out=None):
         """pbso_eq: the device buffer d_in [C][n_buffers * frames] f32 of the last step through the cascades into d_out (None: the
         engine's own; may be d_in).  Device pointers as integers."""

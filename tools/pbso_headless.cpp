@@ -85,6 +85,10 @@
 //                    is cut at these buffers as --pan cuts it; a buffer's lines are one set, cross-faded over N samples (default
 //                    441; a fade must be over before the next set, else the run ends with the engine's refusal).  One engine only:
 //                    not with --devices; not with --raw.
+//   --eq-schedule    with --eq: every line is scheduled up front at sample <buffer> * frames (pbso_eq_set_at; a buffer's lines are
+//                    one set) and the lines no longer cut the run.  The same samples in the WAV (byte for byte with --time-chunks 1
+//                    on both commands).  The schedule's spacing rule holds from sample 0 on: lines closer than the fade allows, a
+//                    first line before sample N - 1 among them, are refused before anything runs.
 //   --retune FILE    materials changed during the run (pbso_set_material; with --devices pbso_group_set_material): lines
 //                    <buffer> <copy> <material file> [keep|zero] give copy the file's material (the format of -t) from that
 //                    buffer on; keep (the default): the state carries on under the new coefficients, zero: it is cleared.  Every
@@ -105,6 +109,7 @@
 
 #include "openpbso_amd.h"
 #include "resample_clock.h"                              // (openpbso_amd/csrc: the resampler's limits and counts, no HIP in it)
+#include "eq_schedule.h"                                 // (... and its schedule's spacing rule)
 #include "eq_block.h"                                    // (openpbso_amd/csrc: the EQ bus's limits and refusals, no HIP in it)
 
 static void die(const std::string &msg) {
@@ -576,6 +581,7 @@ struct EqScript {
     struct Line { long b; int section, kind; double f0, q, gain; };
     std::vector<Line> lines;
     int S = 0, xfade = 441;
+    bool schedule = false;                               // --eq-schedule: the lines are scheduled up front and cut nothing
     bool on() const { return S > 0; }
     void read(const std::string &path, int n_buffers) {
         static const char *kinds[] = {"lowpass", "highpass", "peak", "lowshelf", "highshelf"};
@@ -600,9 +606,28 @@ struct EqScript {
         }
         if (lines.empty()) die("no lines in " + path);
     }
+    // --eq-schedule: the buffers that have lines, ascending
+    std::vector<long> buffers() const {
+        std::vector<long> b;
+        for (const Line &p : lines) b.push_back(p.b);
+        std::sort(b.begin(), b.end());
+        b.erase(std::unique(b.begin(), b.end()), b.end());
+        return b;
+    }
+    // ... and the schedule's rule on them (pbso_eq_set_at): the identity is a predecessor at sample 0
+    void check_spacing() const {
+        long long t_prev = 0;
+        for (long b : buffers()) {
+            const long long t = (long long)b * PBSO_FRAMES_PER_BUFFER;
+            if (!pbso::eq_spacing_ok(t, t_prev, xfade))
+                die("--eq-schedule: the lines of buffer " + std::to_string(b) + " are closer to their predecessor than the fade allows (--eq-xfade " +
+                    std::to_string(xfade) + ": a set needs t_set - t_prev + 1 >= N, the first one against sample 0)");
+            t_prev = t;
+        }
+    }
     std::vector<int> cut(std::vector<int> cuts, int n_buffers) const {
         for (const Line &p : lines)
-            if (p.b > 0 && p.b < n_buffers) cuts.push_back((int)p.b);
+            if (!schedule && p.b > 0 && p.b < n_buffers) cuts.push_back((int)p.b);
         std::sort(cuts.begin(), cuts.end());
         cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
         return cuts;
@@ -685,9 +710,11 @@ int main(int argc, char **argv) {
         else if (a == "--rs-cutoff") { rs_flag = true; rs_cutoff = std::atof(val().c_str()); }
         else if (a == "--eq") eq_arg = val();
         else if (a == "--eq-xfade") { eq_flag = true; eq.xfade = std::atoi(val().c_str()); }
+        else if (a == "--eq-schedule") eq.schedule = true;
         else die("unknown flag " + a);
     }
     if (eq_flag && eq_arg.empty()) die("--eq-xfade belongs to --eq FILE");
+    if (eq.schedule && eq_arg.empty()) die("--eq-schedule needs --eq FILE: it schedules that script's lines");
     if (!eq_arg.empty()) {
         if (!devices_arg.empty()) die("--eq runs on one engine, not through a device group (--devices)");
         if (!raw.empty()) die("--raw dumps the unscaled mix: not with --eq");
@@ -695,6 +722,7 @@ int main(int argc, char **argv) {
             die("--eq needs --channels C (1 .. 8) and one of --pan FILE or --fir FILE: it filters that mix");
         if (eq.xfade < 0 || eq.xfade > (1 << 20)) die("--eq-xfade must be 0 .. 1048576");
         eq.read(eq_arg, n_buffers);
+        if (eq.schedule) eq.check_spacing();
     }
     if (pcm16 && !limit) die("--pcm16 needs --limit T: an integer WAV clips without a ceiling");
     if (master_flag && !limit) die("--lookahead, --hold and --gain belong to --limit T");
@@ -1099,10 +1127,18 @@ int main(int argc, char **argv) {
         // --eq: the lines of buffer b, given to every channel, before the step that begins there
         auto eq_set_at = [&](int b) {
             std::vector<double> one(eq_sos.begin(), eq_sos.begin() + (size_t)eq.S * 5);
-            if (!eq.on() || !eq.set_at(b, one)) return;
+            if (!eq.on() || eq.schedule || !eq.set_at(b, one)) return;
             for (int c = 0; c < channels_out; ++c) std::copy(one.begin(), one.end(), eq_sos.begin() + (size_t)c * eq.S * 5);
             check(e, pbso_eq_set(e, eq_sos.data()), "eq_set");
         };
+        // --eq-schedule: every buffer that has lines, in order, as one set at its first sample
+        if (eq.on() && eq.schedule)
+            for (long b : eq.buffers()) {
+                std::vector<double> one(eq_sos.begin(), eq_sos.begin() + (size_t)eq.S * 5);
+                eq.set_at(b, one);
+                for (int c = 0; c < channels_out; ++c) std::copy(one.begin(), one.end(), eq_sos.begin() + (size_t)c * eq.S * 5);
+                check(e, pbso_eq_set_at(e, (int64_t)b * PBSO_FRAMES_PER_BUFFER, eq_sos.data()), "eq_set_at");
+            }
         auto master_segment = [&](std::vector<float> &seg) {         // seg [C][row], the last step's
             float *in = (float *)m_in;
             for (size_t i = 0; i < seg.size(); ++i) in[i] = (float)((double)seg[i] / 1E10);
