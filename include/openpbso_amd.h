@@ -943,6 +943,77 @@ int pbso_eq_schedule(pbso_engine *e, int n_sets, const int64_t *t_set, const dou
 int pbso_eq_clear_schedule(pbso_engine *e);             /* drops the sets not yet in force */
 int pbso_eq_schedule_info(pbso_engine *e, int64_t out[4]);
 
+/* Loudness bus: programme loudness and true peak -- ITU-R BS.1770-4 K-weighted energies and the gating of EBU Tech 3341
+ * (momentary, short-term, integrated) on a device buffer [C][n] (what the mixers, the reverb, the EQ and the master bus write), so
+ * that a render can be brought to a delivery target (-23 LUFS for EBU R128, -14 or -16 for streaming) without bringing the audio to
+ * the host.  The stage reads its input and writes no audio.  Every record is bit-reproducible and independent of how the samples
+ * are cut into steps.
+ * Clock and hop: t counts processed samples from the enable or the last reset, 64-bit; u_c(t) is input channel c, 0 for t < 0.  The
+ * hop is Hs = rate / 10 samples (100 ms), rate the engine's sample_rate, which must be a multiple of 10 with Hs >= 256, else
+ * PBSO_ERR_INVALID.  Sub-block j covers t in [j Hs, (j + 1) Hs).
+ * K-weighting: two sections.  pbso_loudness_design(rate, out[2][5]) computes them in fp64 exactly as written here and needs no
+ * engine (rate finite and above twice the shelf's f0, else PBSO_ERR_INVALID).
+ *   stage 1, the shelf: f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196,
+ *     K = tan(pi f0 / rate), Vh = pow(10, G / 20), Vb = pow(Vh, 0.4996667741545416), a0 = 1 + K/Q + K K,
+ *     b0 = (Vh + Vb K/Q + K K) / a0, b1 = 2 (K K - Vh) / a0, b2 = (Vh - Vb K/Q + K K) / a0,
+ *     a1 = 2 (K K - 1) / a0, a2 = (1 - K/Q + K K) / a0
+ *   stage 2, the high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 as above,
+ *     b = 1, -2, 1 (not normalised, as the standard has it), a1 = 2 (K K - 1) / a0, a2 = (1 - K/Q + K K) / a0
+ * At 48000 Hz this is the standard's table to 9e-16.  The weighted signal z_c(t) is signal 2 of the EQ bus's block form with these
+ * two sections on every channel: P = PBSO_EQ_BLOCK, the tables built as the EQ bus builds them, t_set = 0, installed at enable and
+ * never changed, kept in fp64 and not rounded to f32; the state is the EQ's P + 2 fp64 samples per signal.
+ * Energy of a sub-block, in a prescribed order: with k = t - j Hs and l = k mod 64 there are 64 accumulators per channel, which
+ * start at 0.0;  acc_l = fma(z, z, acc_l)  in ascending k; when the sub-block is complete, for s = 32, 16, 8, 4, 2, 1 and every
+ * l < s:  acc_l = acc_l + acc_{l+s};  E_c(j) = acc_0.  The device keeps the 64 accumulators per channel across steps.
+ * True peak (with true_peak != 0 at enable; without it both peaks of every record are 0): the oversampling factor is O = 4 for a
+ * rate below 80 000 Hz and 2 from there up, with T = 12 taps per phase.  The phase table h[O][12] f32 follows the resampler bus's
+ * prototype rule (g[j], h[phi][k] = (float)g[k L + phi]) with L = O, M = 1, beta = 8.0, cutoff = 1.0; it is built once on the host
+ * at enable, and pbso_loudness_taps reads it back.  For every t and phi:
+ *     acc = 0.f; for k = 11 down to 0: acc = fmaf(h[phi][k], u_c(t - k), acc)
+ * TP_c(j) is the maximum of fabsf(acc) over the sub-block's t and all phi, SP_c(j) the maximum of fabsf(u_c(t)).  The device keeps
+ * the last 11 input samples per channel and the running maxima of an open sub-block.  Subnormals are kept.  A non-finite input
+ * leaves later records unspecified.
+ * Log: each complete sub-block appends one record per channel to a device-resident log [max_blocks][C] of pbso_loudness_block;
+ * record j is sub-block j.  A step whose records would not fit is refused with PBSO_ERR_STATE before anything changes.
+ * Report: host fp64 over the log, reachable without an engine through pbso_loudness_report_from_blocks(blocks [n_blocks][C],
+ * n_blocks, C, weight, hop, out).  For gating block i >= 3:  ms_c = (((E_c(i-3) + E_c(i-2)) + E_c(i-1)) + E_c(i)) / (4 Hs);
+ * w_i is the sum over ascending c of G_c ms_c;  l_i = -0.691 + 10 log10(w_i), -infinity for w_i = 0.  The gates:
+ * A = {i : l_i > -70};  Gamma = -0.691 + 10 log10(mean of w over A, ascending i) - 10 (relative_threshold);
+ * integrated = -0.691 + 10 log10(mean of w over {i in A : l_i > Gamma}), n_gated the size of that set.  Momentary is l of the last
+ * gating block; short-term is the same over the last 30 sub-blocks, summed left-associated in ascending order and divided by 30 Hs;
+ * max_momentary and max_short_term are their maxima over the log; true_peak and sample_peak are the maxima of the records' (linear,
+ * over all channels).  Whatever has too few blocks, or an empty gate, is -HUGE_VAL.  The channel weights G_c are doubles, finite
+ * and >= 0, given at enable; NULL means all 1.
+ * pbso_loudness processes n = the last step's n_buffers * frames_per_buffer samples: d_in [C][n] f32 on the device, required and
+ * read only.  Asynchronous on the engine's stream.  While enabled, every step is processed exactly once: a second call for the same
+ * step, a call after a step that was skipped or a call before any step is PBSO_ERR_STATE.  A refused call changes nothing.  The
+ * reset empties the log, silences every state, sets t = 0 and arms the stage for the next step.  pbso_read_loudness_blocks copies
+ * records [first, first + n) of the log, [n][C], synchronous; a range beyond the logged blocks is PBSO_ERR_INVALID.  The stage knows
+ * nothing of the other buses.  A device group has none.                                                                          */
+typedef struct pbso_loudness_block {
+    double energy;       /* E_c(j) */
+    float true_peak;     /* TP_c(j), linear */
+    float sample_peak;   /* SP_c(j), linear */
+} pbso_loudness_block;   /* 16 bytes */
+typedef struct pbso_loudness_summary {
+    double integrated, momentary, short_term;   /* LUFS */
+    double max_momentary, max_short_term;       /* LUFS */
+    double relative_threshold;                  /* Gamma, LUFS */
+    double true_peak, sample_peak;              /* linear; 20 log10 of them is dBTP / dBFS */
+    int64_t n_blocks, n_gated;
+} pbso_loudness_summary; /* 80 bytes */
+int pbso_loudness_enable(pbso_engine *e, int n_channels, const double *weight, int max_blocks, int true_peak);   /* after finalize; n_channels 1 .. 8; weight [C] or NULL; max_blocks 1 .. 1 << 22 */
+int pbso_loudness(pbso_engine *e, const void *d_in);                         /* n = last step's n_buffers * frames_per_buffer; [C][n] f32, read only */
+int pbso_read_loudness_blocks(pbso_engine *e, int64_t first, int64_t n, pbso_loudness_block *out);   /* [n][C], synchronous */
+int pbso_loudness_report(pbso_engine *e, pbso_loudness_summary *out);          /* over the whole log, synchronous */
+int pbso_loudness_taps(pbso_engine *e, float *out, size_t n);                /* the phase table [O][12]; n = O * 12 */
+int pbso_loudness_reset(pbso_engine *e);
+/* out[0] = t of the next processed sample, out[1] = blocks logged, out[2] = steps processed, out[3] = max_blocks */
+int pbso_loudness_info(pbso_engine *e, int64_t out[4]);
+int pbso_loudness_design(double rate, double out[2][5]);
+int pbso_loudness_report_from_blocks(const pbso_loudness_block *blocks, int64_t n_blocks, int n_channels, const double *weight, int hop,
+                                     pbso_loudness_summary *out);
+
 /* --- device group ("create/destroy engine (sample rate, buffer size 513, device list)", 8(e)) -------------
  * Objects are independent -- every ModalSolver owns its integrator state, force list and maps, modal_solver.h:100-126 -- so
  * a job of many objects shards over the GPUs of a node with no exchange while stepping: each RANK (one GPU, one engine) owns a

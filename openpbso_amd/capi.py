@@ -61,6 +61,9 @@ EXPORTS = [
     "pbso_eq_enable", "pbso_eq_set", "pbso_eq", "pbso_read_eq", "pbso_eq_tables", "pbso_eq_reset", "pbso_eq_info", "pbso_eq_design",
     # ... and its schedule (sets at absolute samples, any number of them inside one step)
     "pbso_eq_set_at", "pbso_eq_schedule", "pbso_eq_clear_schedule", "pbso_eq_schedule_info",
+    # the loudness bus (BS.1770 energies and true peaks per 100 ms of a bus [C][n], logged on the device; the gating on the host)
+    "pbso_loudness_enable", "pbso_loudness", "pbso_read_loudness_blocks", "pbso_loudness_report", "pbso_loudness_taps",
+    "pbso_loudness_reset", "pbso_loudness_info", "pbso_loudness_design", "pbso_loudness_report_from_blocks",
     # the device group (one engine per GPU, RCCL gather called from C++)
     "pbso_group_unique_id", "pbso_group_create", "pbso_group_destroy", "pbso_group_last_error", "pbso_group_plan",
     "pbso_group_rank_span", "pbso_group_owner", "pbso_group_add_object", "pbso_group_finalize", "pbso_group_engine",
@@ -136,6 +139,18 @@ class MasterMeter(C.Structure):
 class ResampleMeter(C.Structure):
     """pbso_resample_meter: one record per channel of a pbso_resample call, 8 bytes"""
     _fields_ = [("out_peak", C.c_float), ("n_over", C.c_int32)]
+
+
+class LoudnessBlock(C.Structure):
+    """pbso_loudness_block: one record per (sub-block of 100 ms, channel) of the loudness bus's log, 16 bytes"""
+    _fields_ = [("energy", C.c_double), ("true_peak", C.c_float), ("sample_peak", C.c_float)]
+
+
+class LoudnessSummary(C.Structure):
+    """pbso_loudness_summary: what pbso_loudness_report fills, 80 bytes"""
+    _fields_ = [("integrated", C.c_double), ("momentary", C.c_double), ("short_term", C.c_double), ("max_momentary", C.c_double),
+                ("max_short_term", C.c_double), ("relative_threshold", C.c_double), ("true_peak", C.c_double),
+                ("sample_peak", C.c_double), ("n_blocks", C.c_int64), ("n_gated", C.c_int64)]
 
 
 class EngineInfo(C.Structure):
@@ -329,6 +344,16 @@ def lib():
         l.pbso_eq_schedule.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp]
         l.pbso_eq_clear_schedule.argtypes = [vp]
         l.pbso_eq_schedule_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_loudness"):
+        l.pbso_loudness_enable.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int]
+        l.pbso_loudness.argtypes = [vp, vp]
+        l.pbso_read_loudness_blocks.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(LoudnessBlock)]
+        l.pbso_loudness_report.argtypes = [vp, C.POINTER(LoudnessSummary)]
+        l.pbso_loudness_taps.argtypes = [vp, fp, C.c_size_t]
+        l.pbso_loudness_reset.argtypes = [vp]
+        l.pbso_loudness_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        l.pbso_loudness_design.argtypes = [C.c_double, dp]
+        l.pbso_loudness_report_from_blocks.argtypes = [C.POINTER(LoudnessBlock), C.c_int64, C.c_int, dp, C.c_int, C.POINTER(LoudnessSummary)]
     if "PBSO_LIB" not in os.environ or hasattr(l, "pbso_set_material"):
         l.pbso_set_material.argtypes = [vp, C.c_int, ip, C.POINTER(Material), C.c_int]
         l.pbso_get_material.argtypes = [vp, C.c_int, C.POINTER(Material)]
@@ -378,3 +403,38 @@ def eq_design(kind, rate, f0, q=0.7071067811865476, gain_db=0.0):
     if rc != 0:
         raise ValueError(f"pbso_eq_design({kind!r}, {rate}, {f0}, {q}, {gain_db}): status {rc}")
     return [float(v) for v in out]
+
+
+LOUDNESS_BLOCK = [("energy", "<f8"), ("true_peak", "<f4"), ("sample_peak", "<f4")]      # pbso_loudness_block as a numpy dtype
+
+
+def loudness_design(rate):
+    """pbso_loudness_design: the two K-weighting sections of BS.1770 at `rate`, [2][5] = b0 b1 b2 a1 a2 as doubles"""
+    out = (C.c_double * 10)()
+    rc = lib().pbso_loudness_design(rate, out)
+    if rc != 0:
+        raise ValueError(f"pbso_loudness_design({rate}): status {rc}")
+    return [[float(out[5 * s + k]) for k in range(5)] for s in range(2)]
+
+
+def loudness_summary(r):
+    """a LoudnessSummary as a dict"""
+    return {k: getattr(r, k) for k, _ in LoudnessSummary._fields_}
+
+
+def loudness_report_from_blocks(blocks, hop, weight=None):
+    """pbso_loudness_report_from_blocks: the gating of BS.1770 / Tech 3341 over blocks [n_blocks][C] (a structured array of
+    LOUDNESS_BLOCK, or anything with the fields energy, true_peak, sample_peak); hop = rate / 10; weight [C] or None (all 1)"""
+    import numpy as np
+    b = np.ascontiguousarray(blocks, dtype=np.dtype(LOUDNESS_BLOCK))
+    if b.ndim != 2:
+        raise ValueError("blocks must be [n_blocks][n_channels]")
+    w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+    if w is not None and w.size != b.shape[1]:
+        raise ValueError("weight must be [n_channels]")
+    out = LoudnessSummary()
+    rc = lib().pbso_loudness_report_from_blocks(b.ctypes.data_as(C.POINTER(LoudnessBlock)), b.shape[0], b.shape[1],
+                                                None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)), int(hop), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"pbso_loudness_report_from_blocks: status {rc}")
+    return loudness_summary(out)

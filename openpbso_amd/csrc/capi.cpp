@@ -929,6 +929,62 @@ int pbso_eq_schedule_info(pbso_engine *e, int64_t out[4]) {
 
 // (pbso_eq_design is in eq.cpp: its arithmetic is compiled without FMA contraction)
 
+int pbso_loudness_enable(pbso_engine *e, int n_channels, const double *weight, int max_blocks, int true_peak) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->loudness_enable(n_channels, weight, max_blocks, true_peak);
+    GUARD_END(e)
+}
+
+int pbso_loudness(pbso_engine *e, const void *d_in) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->loudness(d_in);
+    GUARD_END(e)
+}
+
+int pbso_read_loudness_blocks(pbso_engine *e, int64_t first, int64_t n, pbso_loudness_block *out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->read_loudness_blocks(first, n, out);
+    GUARD_END(e)
+}
+
+int pbso_loudness_report(pbso_engine *e, pbso_loudness_summary *out) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->loudness_report(out);
+    GUARD_END(e)
+}
+
+int pbso_loudness_taps(pbso_engine *e, float *out, size_t n) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->loudness_taps(out, n);
+    GUARD_END(e)
+}
+
+int pbso_loudness_reset(pbso_engine *e) {
+    NEED(e);
+    GUARD_BEGIN
+    { int drc_ = e->impl->drain_submit(); if (drc_ != PBSO_OK) return drc_; }
+    return e->impl->loudness_reset();
+    GUARD_END(e)
+}
+
+int pbso_loudness_info(pbso_engine *e, int64_t out[4]) {
+    NEED(e);
+    GUARD_BEGIN
+    return e->impl->loudness_info(out);
+    GUARD_END(e)
+}
+
+// (pbso_loudness_design and pbso_loudness_report_from_blocks are in loudness.cpp, for the same reason)
+
 int pbso_step_to_host(pbso_engine *e, int n_buffers, float *host_out, size_t n_floats) {
     NEED(e);
     GUARD_BEGIN

@@ -289,6 +289,7 @@ Engine::~Engine() {
     master_release();
     resample_release();
     eq_release();
+    loudness_release();
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (aux_stream_) (void)hipStreamSynchronize(aux_stream_);
     if (timeline_have_base_) {                         // (the reference launch's quad was kept out of the free list)

@@ -31,6 +31,7 @@ struct SceneReverb;      // scene_reverb.cpp
 struct Master;           // master.cpp
 struct Resample;         // resample.cpp
 struct Eq;               // eq.cpp
+struct Loudness;         // loudness.cpp
 struct TrackPool;        // track_pool.cpp
 struct BusOut;           // bus_state.h
 struct BusWords;         // bus_clock.h
@@ -328,6 +329,14 @@ public:
     int eq_tables(double *out, size_t n);
     int eq_reset();
     int eq_info(int64_t out[4]);
+    // the loudness bus (loudness.cpp, kernels_loudness.hip): BS.1770 energies and true peaks per 100 ms of a caller's bus [C][n], logged on the device
+    int loudness_enable(int n_channels, const double *weight, int max_blocks, int true_peak);
+    int loudness(const void *d_in);
+    int read_loudness_blocks(int64_t first, int64_t n, pbso_loudness_block *out);
+    int loudness_report(pbso_loudness_summary *out);
+    int loudness_taps(float *out, size_t n);
+    int loudness_reset();
+    int loudness_info(int64_t out[4]);
     int object_n_maps(int obj);
     int set_use_transfer(int obj, int use, int64_t not_before);
     int get_latest_transfer(int obj, double *out);
@@ -606,6 +615,8 @@ private:
     Eq *eq_ = nullptr;                                   // pbso_eq_enable
     void eq_release();
     int eq_scheduled(const void *d_in, void *d_out);     // a step with scheduled sets inside it
+    Loudness *loudness_ = nullptr;                       // pbso_loudness_enable
+    void loudness_release();
     std::atomic<size_t> n_slots_{0};
 
     // per-launch plan, double-buffered (host pinned + device copies)

@@ -484,6 +484,17 @@ int launch_eq_scheduled(const float *in, int C, int S, long long n, int R, const
                         int n_fblk, const double *tab2, const double *pool, const double *hist_to, const double *hist_from, double *next_to,
                         double *next_from, int from_hist, int vs_last, double *work, float *out, hipStream_t stream);
 
+// pbso_loudness (kernels_loudness.hip; loudness_gate.h has the grid of sub-blocks): the energies of the sub-blocks a step touches.  z:
+// the K-weighted rows (launch_eq_cascade's result: z_stride = EQ_HIST + n, z_off = EQ_HIST); hs the hop, k0 where the step's first
+// sample lies in its sub-block, n_touched = (k0 + n - 1) / hs + 1; carry / carry_next [C][64] and peaks / peaks_next [C][2] the open
+// sub-block's accumulators and maxima before / behind the step; log_j0 the record of the first touched sub-block, channel 0.
+int launch_loudness_energy(const double *z, long long z_stride, long long z_off, int C, long long n, int hs, int k0, long long n_touched,
+                           const double *carry, double *carry_next, const unsigned *peaks, unsigned *peaks_next, void *log_j0, hipStream_t stream);
+// the true and sample peaks of in [C][n] merged into what launch_loudness_energy wrote, so behind it on the stream; O = 2 or 4, h [O][12];
+// tail / tail_next [C][11] the input samples before / behind the step
+int launch_loudness_peak(const float *in, int C, long long n, int hs, int k0, int O, const float *tail, float *tail_next, const float *h,
+                         unsigned *peaks_next, void *log_j0, hipStream_t stream);
+
 // One wave that stores `value` (system scope, release) into signal memory: behind the last kernel of a stream's batch it tells a
 // hipStreamWaitValue64 of another stream that the batch is done -- half the latency of an event (scripts/microbench/wait_value.hip)
 int launch_signal_value(unsigned long long *sig, unsigned long long value, hipStream_t stream);

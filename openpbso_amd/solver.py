@@ -996,6 +996,54 @@ class Engine:
         self._chk(self._l.pbso_eq_info(self._h, v))
         return {"t": v[0], "fade_end": v[1], "calls": v[2], "sets": v[3]}
 
+    # -- loudness bus: BS.1770 energies and true peaks per 100 ms of a device buffer [C][n], logged on the device ----------------
+    def loudness_enable(self, n_channels, weight=None, max_blocks=36000, true_peak=True):
+        """pbso_loudness_enable: weight [C] doubles or None (all 1); max_blocks records of 100 ms per channel (36000 is an hour);
+        from the next step on, every step is measured exactly once (loudness)"""
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        if w is not None and w.size != n_channels:
+            raise PbsoError(capi.ERR_INVALID, "loudness_enable: weight must be [n_channels]")
+        self._chk(self._l.pbso_loudness_enable(self._h, n_channels, None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)),
+                                               max_blocks, 1 if true_peak else 0))
+        self._loud_channels = n_channels
+
+    def loudness(self, d_in):
+        """pbso_loudness: measures the device buffer d_in [C][n_buffers * frames] f32 of the last step (read only).  A device
+        pointer as an integer."""
+        self._chk(self._l.pbso_loudness(self._h, None if d_in is None else C.c_void_p(d_in)))
+
+    def read_loudness_blocks(self, first=0, n=None):
+        """records [first, first + n) of the log (n None: all behind first): a structured array [n][C] (energy, true_peak, sample_peak)"""
+        if n is None:
+            n = self.loudness_info()["blocks"] - first
+        channels = getattr(self, "_loud_channels", 1)                # (not enabled yet: the call itself says so)
+        out = np.empty((max(n, 0), channels), dtype=np.dtype(capi.LOUDNESS_BLOCK))
+        self._chk(self._l.pbso_read_loudness_blocks(self._h, first, n, out.ctypes.data_as(C.POINTER(capi.LoudnessBlock))))
+        return out
+
+    def loudness_report(self):
+        """pbso_loudness_report: integrated, momentary, short_term, their maxima, relative_threshold (LUFS), true_peak and
+        sample_peak (linear), n_blocks, n_gated"""
+        r = capi.LoudnessSummary()
+        self._chk(self._l.pbso_loudness_report(self._h, C.byref(r)))
+        return capi.loudness_summary(r)
+
+    def loudness_taps(self):
+        """the true peak's phase table: [O][12] float32, O = 4 below 80 kHz and 2 from there up"""
+        O = 4 if self.sample_rate < 80000 else 2
+        out = np.empty((O, 12), dtype=np.float32)
+        self._chk(self._l.pbso_loudness_taps(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def loudness_reset(self):
+        self._chk(self._l.pbso_loudness_reset(self._h))
+
+    def loudness_info(self):
+        """pbso_loudness_info: t of the next measured sample, blocks logged, calls, max_blocks"""
+        v = (C.c_int64 * 4)()
+        self._chk(self._l.pbso_loudness_info(self._h, v))
+        return {"t": v[0], "blocks": v[1], "calls": v[2], "max_blocks": v[3]}
+
     def info(self):
         i = capi.EngineInfo()
         self._chk(self._l.pbso_get_info(self._h, C.byref(i)))

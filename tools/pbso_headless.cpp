@@ -89,6 +89,14 @@
 //                    one set) and the lines no longer cut the run.  The same samples in the WAV (byte for byte with --time-chunks 1
 //                    on both commands).  The schedule's spacing rule holds from sample 0 on: lines closer than the fade allows, a
 //                    first line before sample N - 1 among them, are refused before anything runs.
+//   --loudness FILE [--loudness-target T]   the loudness bus (pbso_loudness) on what the tool writes, at the engine's rate: the mono
+//                    object mix, --pan, --fir, dry + wet with --reverb, behind --eq when that is given.  FILE gets `key value` lines,
+//                    %.17g: the report of pbso_loudness_report (integrated, momentary, short_term, max_momentary, max_short_term,
+//                    relative_threshold in LUFS; true_peak and sample_peak linear; n_blocks, n_gated), target and gain_to_target =
+//                    pow(10, (T - integrated) / 20) (T in LUFS, default -23), then every record of the log as energy.<j>.<c>,
+//                    true_peak.<j>.<c>, sample_peak.<j>.<c>.  Only whole sub-blocks of 100 ms count.  The workflow is: measure, then
+//                    render again with --limit ... --gain G.  One engine only: not with --devices; not with --limit, --out-rate
+//                    (it would measure in front of them) or --raw.
 //   --retune FILE    materials changed during the run (pbso_set_material; with --devices pbso_group_set_material): lines
 //                    <buffer> <copy> <material file> [keep|zero] give copy the file's material (the format of -t) from that
 //                    buffer on; keep (the default): the state carries on under the new coefficients, zero: it is cleared.  Every
@@ -111,6 +119,7 @@
 #include "resample_clock.h"                              // (openpbso_amd/csrc: the resampler's limits and counts, no HIP in it)
 #include "eq_schedule.h"                                 // (... and its schedule's spacing rule)
 #include "eq_block.h"                                    // (openpbso_amd/csrc: the EQ bus's limits and refusals, no HIP in it)
+#include "loudness_gate.h"                               // (openpbso_amd/csrc: the loudness bus's hop, no HIP in it)
 
 static void die(const std::string &msg) {
     std::fprintf(stderr, "pbso_headless: %s\n", msg.c_str());
@@ -645,7 +654,9 @@ struct EqScript {
 };
 
 int main(int argc, char **argv) {
-    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_dirs, fir_bank, fir_delay, reverb, strokes_file, arprm_arg, retune_arg, eq_arg;
+    std::string d, name, mesh, modes, material, ffat, hits, track_hits, listener, out = "out.wav", raw, devices_arg, pan, fir, fir_dirs, fir_bank, fir_delay, reverb, strokes_file, arprm_arg, retune_arg, eq_arg, loudness_arg;
+    double loudness_target = -23.0;
+    bool loudness_flag = false;                          // --loudness-target was given
     EqScript eq;
     bool eq_flag = false;                                // --eq-xfade was given
     StrokeScript strokes;
@@ -711,6 +722,8 @@ int main(int argc, char **argv) {
         else if (a == "--eq") eq_arg = val();
         else if (a == "--eq-xfade") { eq_flag = true; eq.xfade = std::atoi(val().c_str()); }
         else if (a == "--eq-schedule") eq.schedule = true;
+        else if (a == "--loudness") loudness_arg = val();
+        else if (a == "--loudness-target") { loudness_flag = true; loudness_target = std::atof(val().c_str()); }
         else die("unknown flag " + a);
     }
     if (eq_flag && eq_arg.empty()) die("--eq-xfade belongs to --eq FILE");
@@ -724,6 +737,15 @@ int main(int argc, char **argv) {
         eq.read(eq_arg, n_buffers);
         if (eq.schedule) eq.check_spacing();
     }
+    if (loudness_flag && loudness_arg.empty()) die("--loudness-target belongs to --loudness FILE");
+    if (!loudness_arg.empty()) {
+        if (!devices_arg.empty()) die("--loudness runs on one engine, not through a device group (--devices)");
+        if (!raw.empty()) die("--raw dumps the unscaled mix: not with --loudness");
+        if (limit) die("--loudness measures in front of the limiter: not with --limit (measure, then render again with --limit T --gain G)");
+        if (out_rate) die("--loudness measures at the engine's rate: not with --out-rate");
+        if (!(std::isfinite(loudness_target) && loudness_target >= -70.0 && loudness_target <= 0.0)) die("--loudness-target must be -70 .. 0 LUFS");
+    }
+    const bool loud = !loudness_arg.empty();
     if (pcm16 && !limit) die("--pcm16 needs --limit T: an integer WAV clips without a ceiling");
     if (master_flag && !limit) die("--lookahead, --hold and --gain belong to --limit T");
     if (limit) {
@@ -1106,7 +1128,7 @@ int main(int argc, char **argv) {
             while (pbso::resample_max_out((long long)(n_buffers + n_tail) * PBSO_FRAMES_PER_BUFFER, rs_L, rs_M) < rs_drop + rs_keep) ++n_tail;
         }
         const int n_run = n_buffers + n_tail;
-        const bool post = limit || out_rate || eq.on();      // the segments go through a bus behind the mix
+        const bool post = limit || out_rate || eq.on() || loud;      // the segments go through a bus behind the mix
         void *m_in = nullptr;
         if (post && pbso_host_alloc((size_t)channels_out * n_run * PBSO_FRAMES_PER_BUFFER * sizeof(float), &m_in) != PBSO_OK)
             die("cannot allocate the master bus's input");
@@ -1118,6 +1140,9 @@ int main(int argc, char **argv) {
             check(e, pbso_resample_enable(e, channels_out, out_rate, rs_taps, rs_beta, rs_cutoff), "resample_enable");
             resampled.resize(channels_out);
         }
+        const int loud_hop = pbso::loudness_hop(PBSO_SAMPLE_RATE);
+        if (loud)
+            check(e, pbso_loudness_enable(e, channels_out, nullptr, (int)((long long)n_run * PBSO_FRAMES_PER_BUFFER / loud_hop) + 1, 1), "loudness_enable");
         std::vector<double> eq_sos;                          // --eq: [C][S][5], every channel alike
         if (eq.on()) {
             check(e, pbso_eq_enable(e, channels_out, eq.S, eq.xfade), "eq_enable");
@@ -1144,8 +1169,11 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < seg.size(); ++i) in[i] = (float)((double)seg[i] / 1E10);
             // --eq in place, in front of the limiter and the resampler
             if (eq.on()) check(e, pbso_eq(e, m_in, m_in), "eq");
+            // --loudness behind it, on the samples of the WAV
+            if (loud) check(e, pbso_loudness(e, m_in), "loudness");
             if (!limit && !out_rate) {
-                check(e, pbso_read_eq(e, seg.data(), seg.size()), "read_eq");
+                if (eq.on()) check(e, pbso_read_eq(e, seg.data(), seg.size()), "read_eq");
+                else check(e, pbso_sync(e), "sync");                 // (the next segment overwrites the bus's input; seg stays the unscaled mix)
                 return;
             }
             if (out_rate) {
@@ -1280,6 +1308,28 @@ int main(int argc, char **argv) {
             }
         }
         if (post) check(e, pbso_sync(e), "sync");
+        if (loud) {
+            pbso_loudness_summary r;
+            check(e, pbso_loudness_report(e, &r), "loudness_report");
+            std::vector<pbso_loudness_block> blocks((size_t)r.n_blocks * channels_out);
+            check(e, pbso_read_loudness_blocks(e, 0, r.n_blocks, blocks.data()), "read_loudness_blocks");
+            FILE *f = std::fopen(loudness_arg.c_str(), "w");
+            if (!f) die("cannot write " + loudness_arg);
+            const double values[8] = {r.integrated, r.momentary, r.short_term, r.max_momentary, r.max_short_term, r.relative_threshold, r.true_peak, r.sample_peak};
+            const char *keys[8] = {"integrated", "momentary", "short_term", "max_momentary", "max_short_term", "relative_threshold", "true_peak", "sample_peak"};
+            for (int k = 0; k < 8; ++k) std::fprintf(f, "%s %.17g\n", keys[k], values[k]);
+            std::fprintf(f, "n_blocks %lld\nn_gated %lld\n", (long long)r.n_blocks, (long long)r.n_gated);
+            std::fprintf(f, "target %.17g\ngain_to_target %.17g\n", loudness_target, std::pow(10.0, (loudness_target - r.integrated) / 20.0));
+            for (long long j = 0; j < (long long)r.n_blocks; ++j)
+                for (int c = 0; c < channels_out; ++c) {
+                    const pbso_loudness_block &b = blocks[(size_t)j * channels_out + c];
+                    std::fprintf(f, "energy.%lld.%d %.17g\ntrue_peak.%lld.%d %.17g\nsample_peak.%lld.%d %.17g\n", j, c, b.energy, j, c, (double)b.true_peak, j, c,
+                                 (double)b.sample_peak);
+                }
+            std::fclose(f);
+            std::printf("loudness: integrated %.2f LUFS, true peak %.2f dBTP, gain to %.1f LUFS %.4f -> %s\n", r.integrated,
+                        20.0 * std::log10(r.true_peak), loudness_target, std::pow(10.0, (loudness_target - r.integrated) / 20.0), loudness_arg.c_str());
+        }
         pbso_host_free(m_in);
         pbso_engine_info info;
         check(e, pbso_get_info(e, &info), "get_info");
